@@ -10,7 +10,16 @@ value = CG iterations completed by ALL ranks / max-over-ranks wall time of the K
 solves.  Multi-GPU: one process per GPU (torchrun), each rank solves its own independent
 system (no data-path collective); one RCCL all-reduce of the per-rank timings at the end.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload kuhn101]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload kuhn101] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--dump-outputs DIR``
+also writes what the last timed step returned (the solution x, its iteration count and converged
+flag) as ``DIR/<name>.npy``; the system, the GNN weights and the right-hand side are seeded, so
+two runs with the same arguments solve the same problem.  ``--full`` adds every other measurement
+to the line after the timed steps (GNN timing, the reference's counts, per-launch loop times,
+preconditioner / rhs variants, the SpMV roofline, CPU baselines, C1 / C5, parity mode, the
+irregular 1M-row systems); ``--no-cpu``, ``--no-variants``, ``--cpu-iters``, ``--cpu-all-threads``
+and ``--spmv-reps`` trim or size those legs.
 """
 from __future__ import annotations
 
@@ -26,6 +35,7 @@ import numpy as np
 METRIC = "CG iters/sec + time-to-rel-residual-1e-8; SpMV achieved HBM GB/s vs roofline"
 HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md "Chip-level parameters")
 FLUSH_BYTES = 512 << 20  # > 256 MiB Infinity Cache
+DUMP_MAX_BYTES = 48_000_000  # --dump-outputs: all files together, well under 64 MB
 
 
 def log(*a):
@@ -584,6 +594,23 @@ def config_rows() -> dict:
     return out
 
 
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: each array as ``path/<name>.npy`` in its float32 / float64 dtype (anything
+    else as float64).  The files together stay under DUMP_MAX_BYTES: an array beyond its equal
+    share is cut to a fixed sample (sorted indices drawn once from seed 0, the same for every run
+    of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -592,6 +619,12 @@ def main():
     ap.add_argument("--workload", default="kuhn101")
     ap.add_argument("--epsilon", type=float, default=3e-3)
     ap.add_argument("--rtol", type=float, default=1e-8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline figure: GNN timing, "
+                         "reference counts, per-launch loop times, preconditioner / rhs variants, the SpMV roofline, "
+                         "CPU baselines, C1 / C5, parity mode and the irregular 1M-row systems")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (x, iters, converged) as DIR/<name>.npy")
     ap.add_argument("--cpu-iters", type=int, default=60,
                     help="iterations per bounded CPU baseline solve (1 warm-up + median of 5, at nproc and 1 BLAS threads)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -633,16 +666,19 @@ def main():
     ws = SimpleInferenceWorkspace(node_features=sample.x.shape[1], edge_features=sample.edge_attr.shape[1],
                                   block_size=bs, epsilon=args.epsilon, seed=0)
     dev_sample = sample.to("cuda")
-    for _ in range(2):
-        L, gnn_dt = ws.inference_step(dev_sample)  # warm the GNN (infer.py:270-275)
+    # one forward emits L; --full times the forward (2 warm-ups as infer.py:270-275, then 5 timed)
+    for _ in range(2 if args.full else 0):
+        L, gnn_dt = ws.inference_step(dev_sample)
     gnn_times = []
-    for _ in range(5):
+    for _ in range(5 if args.full else 1):
         L, gnn_dt = ws.inference_step(dev_sample)
         gnn_times.append(gnn_dt)
-    log(f"rank {rank}: GNN forward ms {[round(t * 1e3, 3) for t in gnn_times]}")
-    gnn_fl = gnn_flops(sample.x.shape[0], sample.edge_index.shape[1], sample.x.shape[1], sample.edge_attr.shape[1],
-                       bs * bs)
-    ref_iters = reference_iters(args.workload, ws.forward(dev_sample.x, dev_sample.edge_index, dev_sample.edge_attr))
+    if args.full:
+        log(f"rank {rank}: GNN forward ms {[round(t * 1e3, 3) for t in gnn_times]}")
+    ref_iters = None
+    if args.full:
+        ref_iters = reference_iters(args.workload,
+                                    ws.forward(dev_sample.x, dev_sample.edge_index, dev_sample.edge_attr))
     A = ws.system_matrix(dev_sample)
     n, nnz_a, nnz_l = A.n, A.nnz, L.nnz
     gt = dev_sample.mask.reshape(-1).to(torch.float64)
@@ -679,6 +715,75 @@ def main():
     if world > 1:
         elapsed, total_iters = reduce_timing(elapsed, total_iters, torch.device("cuda", local))
 
+    if args.dump_outputs:  # what the last timed step handed back: x (written in place) and its status
+        tag = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"x" + tag: x.cpu().numpy(), "iters" + tag: np.array([it], dtype=np.float64),
+                                         "converged" + tag: np.array([conv], dtype=np.float64)})
+
+    it_per_solve = iters[-1]
+    t_iter = float(np.median(solve_times)) / max(it_per_solve, 1)
+    extra = {}
+    if args.full:
+        extra = full_rows(args, rank, world, sample, A, L, b, gt, solver, bs, t_iter, float(np.median(gnn_times)))
+        extra.update({
+            "reference_iters": ref_iters,
+            "gnn_precond_ms": float(np.median(gnn_times)) * 1e3,
+            # the reference's "Total Time" row (infer.py:372-384): precond (GNN) + solve; plus the
+            # device Lᵀ / SELL view setup, which the reference does on the host outside its timers
+            "total_ms": (float(np.median(solve_times)) + float(np.median(gnn_times)) + prec_s) * 1e3,
+        })
+
+    if rank == 0:
+        line = {
+            "metric": METRIC,
+            "value": total_iters / elapsed,
+            "unit": "CG iters/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic: Kuhn-tet grid Laplacian (Dirichlet face), seeded random-init GNN weights",
+            "config": {
+                "workload": f"{args.workload}: ext_spai PCG to rel-residual {args.rtol:g}, n={n}, nnz(A)={nnz_a}, "
+                            f"nnz(L)={nnz_l}, GNN-inferred L (F=16, 4 MP layers)",
+                "n": n, "nnz_A": nnz_a, "nnz_L": nnz_l, "precond": "ext_spai", "epsilon": args.epsilon,
+                "rtol": args.rtol, "iters_per_solve": it_per_solve, "systems_per_gpu": 1,
+                "parallelism": f"independent systems, 1 per GPU x {world}",
+            },
+            "time_to_rtol_ms": float(np.median(solve_times)) * 1e3,
+            "lt_setup_ms": prec_s * 1e3,
+            "pcg_iter_us": t_iter * 1e6,
+            # SURVEY 8(d) fp64/int32 CSR bytes per iteration / iteration time: the loop READS a
+            # lossless compact format (fp32 values, 16-bit columns) and part of its ~200 MB working
+            # set stays in the 256 MiB Infinity Cache, so this can exceed HBM-achievable rates --
+            # it is a cache-assisted, compact-format figure, not an HBM roofline fraction
+            "pcg_alg_GBs": pcg_bytes_per_iter(n, nnz_a, nnz_l) / t_iter / 1e9,
+            "pcg_alg_GBs_note": "cache-assisted, compact-format figure (SURVEY 8(d) CSR bytes / iteration time)",
+            "solver_views": solver.views,
+            "full": bool(args.full),
+        }
+        line.update(extra)
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_rows(args, rank: int, world: int, sample, A, L, b, gt, solver, bs: int, t_iter: float,
+              gnn_s: float) -> dict:
+    """--full: every measurement beside the headline figure, taken after the timed steps on the
+    same system and solver; returns the result line's further keys."""
+    import torch
+
+    from learningsparsepreconditioner4gpu_amd.linalg import PreconditionedConjugateGradient
+
+    n, nnz_a, nnz_l = A.n, A.nnz, L.nnz
+    gnn_fl = gnn_flops(sample.x.shape[0], sample.edge_index.shape[1], sample.x.shape[1], sample.edge_attr.shape[1],
+                       bs * bs)
+
     # ---- the loop's own launches, each bracketed by HIP events (one untimed 40-iteration pass on
     # the solver stream after the timed region): the dominant kernel against its format bytes
     try:
@@ -687,8 +792,6 @@ def main():
         log(f"rank {rank}: no per-launch loop timing: {e}")
         loop_kernels = {}
     loop_dom = loop_dominant(loop_kernels, A, n, nnz_l) if loop_kernels else None
-
-    views = solver.views
 
     # ---- time-to-rtol beside the neural preconditioner (infer.py:310-321 rows): CG and Jacobi on the
     # same system and rhs, and every method with infer.py's rhs="random" (:300-302, b = A (randn ⊙ mask))
@@ -746,9 +849,6 @@ def main():
     pcg_spmv = pcg_loop_spmv(A, p, q, args.spmv_reps, kind) if A.block_size == 1 and kind else None
     gbs_cold = alg / (ms_cold * 1e-3) / 1e9
     gbs_warm = alg / (ms_warm * 1e-3) / 1e9
-    it_per_solve = iters[-1]
-    t_iter = float(np.median(solve_times)) / max(it_per_solve, 1)
-    pcg_gbs = pcg_bytes_per_iter(n, nnz_a, nnz_l) / t_iter / 1e9
 
     # HBM bytes per launch of the same kernel on the same matrix from the committed PMC passes
     # (tools/spmv_traffic.sh: FETCH_SIZE x2 + WRITE_SIZE, gfx950 correction), if they match
@@ -810,46 +910,13 @@ def main():
             except Exception as e:  # pragma: no cover
                 irregular = {"failed": str(e)}
 
+    out = {}
     if rank == 0:
-        value = total_iters / elapsed
-        line = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "CG iters/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic: Kuhn-tet grid Laplacian (Dirichlet face), seeded random-init GNN weights",
-            "config": {
-                "workload": f"{args.workload}: ext_spai PCG to rel-residual {args.rtol:g}, n={n}, nnz(A)={nnz_a}, "
-                            f"nnz(L)={nnz_l}, GNN-inferred L (F=16, 4 MP layers)",
-                "n": n, "nnz_A": nnz_a, "nnz_L": nnz_l, "precond": "ext_spai", "epsilon": args.epsilon,
-                "rtol": args.rtol, "iters_per_solve": it_per_solve, "systems_per_gpu": 1,
-                "parallelism": f"independent systems, 1 per GPU x {world}",
-            },
-            "reference_iters": ref_iters,
-            "time_to_rtol_ms": float(np.median(solve_times)) * 1e3,
+        out = {
             "time_to_rtol_variants": variants,
-            "gnn_tflops": gnn_fl / float(np.median(gnn_times)) / 1e12,
-            "gnn_tflops_frac_of_157": gnn_fl / float(np.median(gnn_times)) / 157.3e12,
+            "gnn_tflops": gnn_fl / gnn_s / 1e12,
+            "gnn_tflops_frac_of_157": gnn_fl / gnn_s / 157.3e12,
             "gnn_flops_per_forward": gnn_fl,
-            # the reference's "Total Time" row (infer.py:372-384): precond (GNN) + solve; plus the
-            # device Lᵀ / SELL view setup, which the reference does on the host outside its timers
-            "total_ms": (float(np.median(solve_times)) + float(np.median(gnn_times)) + prec_s) * 1e3,
-            "gnn_precond_ms": float(np.median(gnn_times)) * 1e3,
-            "lt_setup_ms": prec_s * 1e3,
-            "pcg_iter_us": t_iter * 1e6,
-            # SURVEY 8(d) fp64/int32 CSR bytes per iteration / iteration time: the loop READS a
-            # lossless compact format (fp32 values, 16-bit columns) and part of its ~200 MB working
-            # set stays in the 256 MiB Infinity Cache, so this can exceed HBM-achievable rates --
-            # it is a cache-assisted, compact-format figure, not an HBM roofline fraction
-            "pcg_alg_GBs": pcg_gbs,
-            "pcg_alg_GBs_note": "cache-assisted, compact-format figure (SURVEY 8(d) CSR bytes / iteration time)",
             "roofline": {
                 "kernel": kernel,
                 "bound": "hbm", "achieved": gbs_cold, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -863,7 +930,6 @@ def main():
                 "method": "cold = a 512 MiB read before every launch; launch time = the SpMV kernel's own start/end stamps (hipExtLaunchKernelGGL events on the ctx stream, the duration rocprofv3's kernel trace reports), averaged over the launches",
             },
             "pcg_loop_spmv": pcg_spmv,
-            "solver_views": views,
             "pcg_loop_kernels": loop_dom,
             "cpu_baseline": cpu,
             "c1_synthetic": c1,
@@ -871,9 +937,7 @@ def main():
             "parity_mode": parity,
             "irregular_1m": irregular,
         }
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

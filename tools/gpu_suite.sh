@@ -17,7 +17,7 @@ for s in $steps; do
       timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.txt" 2>&1 || exit $?
       grep smoke "$out/smoke.txt" ;;
     bench)
-      timeout -k 10 300 python -u bench.py > "$out/bench.json" 2> "$out/bench.err" || exit $?
+      timeout -k 10 300 python -u bench.py --full > "$out/bench.json" 2> "$out/bench.err" || exit $?
       python3 -c "
 import json; d=json.load(open('$out/bench.json')); print(d['value'], d['pcg_iter_us'], d['gnn_precond_ms'], d['roofline']['frac'], d['roofline']['kernel'][:40], d['pcg_loop_kernels']['all_us'])" ;;
     prof)
@@ -31,7 +31,7 @@ import json; d=json.load(open('$out/bench.json')); print(d['value'], d['pcg_iter
       bash tools/spmv_traffic.sh "$tag" || exit $?
       cat "gpurun_out/traffic_$tag/summary.json" ;;
     looptraffic)  # the PCG loop's five launches: FETCH_SIZE / WRITE_SIZE passes over a short bench
-      bash tools/pmc_run.sh "$tag" bench.py --steps 1 --warmup 1 --no-cpu --no-variants -- FETCH_SIZE WRITE_SIZE || exit $?
+      bash tools/pmc_run.sh "$tag" bench.py --full --steps 1 --warmup 1 --no-cpu --no-variants -- FETCH_SIZE WRITE_SIZE || exit $?
       python3 tools/loop_traffic.py "$tag" 1 > "$out/pcg_loop_traffic.json" && cat "$out/pcg_loop_traffic.json"
       find "gpurun_out/pmc_$tag" -name "*.csv" -size +2M -delete ;;
     ab=*)  # interleaved loop A/B: ab='{"base": {}, "x": {"ENV": "1"}}'

@@ -1,5 +1,5 @@
 """Per-launch HBM bytes of the PCG loop's five kernels from two rocprofv3 --pmc passes
-(FETCH_SIZE, WRITE_SIZE) over `bench.py --steps 1 --warmup 1 --no-cpu --no-variants`
+(FETCH_SIZE, WRITE_SIZE) over `bench.py --full --steps 1 --warmup 1 --no-cpu --no-variants`
 (tools/pmc_run.sh <tag> bench.py ... -- FETCH_SIZE WRITE_SIZE), written in the format bench.py
 reads from profiles/pcg_loop_traffic.json.
 
@@ -43,7 +43,7 @@ def main():
             run = json.loads(line)
     out = {"workload": run["config"]["workload"].split(":")[0], "n": run["config"]["n"], "nnz": run["config"]["nnz_A"],
            "column_kind": kind, "source": f"gpurun_out/pmc_{tag}",
-           "method": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, bench.py --steps 1 --warmup 1 --no-cpu "
+           "method": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, bench.py --full --steps 1 --warmup 1 --no-cpu "
                      "--no-variants; bytes = FETCH_SIZE x 2 (gfx950) x 1024 + WRITE_SIZE x 1024, median per dispatch",
            "kernels": {}}
     for k in KERNELS:

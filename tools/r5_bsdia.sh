@@ -12,7 +12,7 @@ rc=$?; tail -3 "$out/bsr_tests.txt"; [ $rc -eq 0 ] || exit $rc
 LOOP_AB_KERNELS=1 LOOP_AB_REPLICAS=2 timeout -k 10 400 python -u tools/loop_ab.py '{"bsdia": {}, "bsell": {"LSPCG_BSDIA": "0"}}' elast 7 "$out/c4_loop_ab.jsonl" > "$out/c4_loop_ab.txt" 2>&1
 rc=$?; cat "$out/c4_loop_ab.txt" | tail -20; [ $rc -eq 0 ] || exit $rc
 for v in 1 0; do
-  LSPCG_BSDIA=$v timeout -k 10 300 python -u bench.py --workload elast --steps 3 --warmup 1 --no-cpu --no-variants > "$out/bench_elast_bsdia$v.json" 2> "$out/bench_elast_bsdia$v.err" || exit $?
+  LSPCG_BSDIA=$v timeout -k 10 300 python -u bench.py --full --workload elast --steps 3 --warmup 1 --no-cpu --no-variants > "$out/bench_elast_bsdia$v.json" 2> "$out/bench_elast_bsdia$v.err" || exit $?
   python3 -c "
 import json; d=json.load(open('$out/bench_elast_bsdia$v.json')); r=d['roofline']; print('bsdia=$v', d['value'], d['pcg_iter_us'], r['frac'], r['avg_launch_ms_cold'], r['kernel'][:30])"
 done

@@ -9,7 +9,7 @@ mkdir -p "$out"
 timeout -k 10 300 python -u tools/sell_sweep.py --bsr > "$out/bsr_sweep.jsonl" 2> "$out/bsr_sweep.err" || exit $?
 cat "$out/bsr_sweep.jsonl"
 for wv in 1 3 1 3; do
-  LSPCG_BSELL_WAVES=$wv timeout -k 10 300 python -u bench.py --workload elast --steps 3 --warmup 1 --no-cpu --no-variants \
+  LSPCG_BSELL_WAVES=$wv timeout -k 10 300 python -u bench.py --full --workload elast --steps 3 --warmup 1 --no-cpu --no-variants \
     > "$out/bench_elast_w$wv.json" 2>> "$out/bench.err" || exit $?
   python3 -c "
 import json; d=json.load(open('$out/bench_elast_w$wv.json')); print('waves $wv', d['value'], d['pcg_iter_us'], d['roofline']['frac'], d['roofline'].get('kernel'), d['pcg_loop_kernels'].get('all_us'))"

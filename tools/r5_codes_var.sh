@@ -10,7 +10,7 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 for r in $(seq 1 $rounds); do
   for v in 0 1; do
-    LSPCG_VALUE_CODES=$v timeout -k 10 200 python -u bench.py --workload kuhn101 --no-cpu --steps 10 --warmup 2 --no-variants > "$out/codes${v}_$r.json" 2>/dev/null || exit $?
+    LSPCG_VALUE_CODES=$v timeout -k 10 200 python -u bench.py --full --workload kuhn101 --no-cpu --steps 10 --warmup 2 --no-variants > "$out/codes${v}_$r.json" 2>/dev/null || exit $?
     python3 -c "
 import json; d=json.load(open('$out/codes${v}_$r.json')); k=d['pcg_loop_kernels']['all_us']
 print(json.dumps({'codes': $v, 'round': $r, 'us_iter': round(d['pcg_iter_us'], 2), 'kernels': {a: round(b, 2) for a, b in k.items()}}))" | tee -a "$out/codes_var.jsonl"

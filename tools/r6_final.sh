@@ -11,7 +11,7 @@ mkdir -p "$out"
 for s in $steps; do
   case $s in
     bench)
-      timeout -k 10 600 python -u bench.py > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
+      timeout -k 10 600 python -u bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
       python3 -c "import json; d=json.load(open('$out/bench.json')); print('bench', d['value'], d['pcg_iter_us'], d['roofline']['frac'])" ;;
     prof)
       bash tools/prof_bench.sh "$tag" || exit $?

@@ -20,7 +20,7 @@ for s in "$@"; do
         timeout -k 10 300 python -u tools/jag_probe.py $wl >> "$out/jag.jsonl" 2>> "$out/jag.err" || { tail -5 "$out/jag.err"; exit 1; }
       done; cat "$out/jag.jsonl" ;;
     bench)
-      timeout -k 10 600 python -u bench.py > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
+      timeout -k 10 600 python -u bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
       python3 -c "
 import json; d=json.load(open('$out/bench.json')); print(d['value'], d['pcg_iter_us'], d['gnn_precond_ms'], d['roofline']['frac'])" ;;
     *) echo "unknown step $s"; exit 2 ;;
