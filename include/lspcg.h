@@ -301,6 +301,39 @@ int lspcg_graph_spmv(lspcg_graph* g, const void* vals, int dtype, int transpose,
  * (t: caller-provided [N*bs] scratch that receives AᵀX, the reference's AT_x) */
 int lspcg_graph_aatpe(lspcg_graph* g, const void* vals, int dtype, double epsilon, const void* x, const void* mask,
                       const void* diag, void* t, void* y);
+/* ---- the training objective and its gradient on the same handle ----
+ * Both calls below keep scratch in the handle (the ends of every edge in the caller's order; six
+ * N*bs vectors and the reduction partials of spai_loss), allocated on first use and freed by
+ * lspcg_graph_destroy: calls on ONE graph handle must run on one stream at a time.  No
+ * floating-point atomics anywhere: the same inputs give the same bits.
+ *
+ * Gradient of one GraphSpmv with respect to its values (what torch autograd derives from PyG's
+ * propagate in basic_layers.py:126-142, there an [E,b,b] message tensor scatter-added with
+ * atomics): for y = mask ⊙ (A x) and gy = mask ⊙ (upstream gradient), already masked by the caller,
+ *   transpose = 0: dvals_e = gy_I ⊗ x_J        transpose = 1 (y = mask ⊙ (Aᵀ x)): dvals_e = x_I ⊗ gy_J
+ * with e = (I, J) = (edge_index[0][e], edge_index[1][e]); dvals [E,bs,bs] in the caller's edge
+ * order, duplicated edges each receive their own gradient.  (The gradient with respect to x is
+ * lspcg_graph_spmv with the opposite transpose flag applied to gy.) */
+int lspcg_graph_spmv_grad_vals(lspcg_graph* g, int dtype, int transpose, const void* gy, const void* x, void* dvals);
+/* The reference's training / validation step after the GNN (workspace.py:96-112 _shared_step,
+ * scaled_workspace.py:98-104 with diag = inv_diag): d = AATPE(epsilon)(r, edge_index, L, mask[, diag]),
+ * then the loss of loss.py on q = mask ⊙ (A d):
+ *   kind 0  RelativeL2Loss_ANorm (loss.py:168-188, sqr_out = True, config/loss.yaml's default):
+ *           (1/B) Σ_g ‖q_g − r_g‖² / (‖r_g‖² + loss_eps) over the graphs ptr[g] .. ptr[g+1] (nodes)
+ *   kind 1  L2Loss_ANorm (loss.py:190-203): the mean of (q − r)² over all N*bs elements
+ * and, when dLvals is not NULL, its gradient with respect to the values of L in the caller's edge
+ * order (dLvals [E,bs,bs]; what loss.backward() leaves in boo_entry.grad):
+ *   gq = 2 (q − r) w_g ; gy = m ⊙ (Aᵀ (m ⊙ gq)) ; gtm = m ⊙ (Lᵀ gy) [⊙ diag] ; dL_e = gy_I ⊗ t_J + r_I ⊗ gtm_J
+ * Lvals / Avals [E,bs,bs], r / mask / diag [N*bs] of `dtype` (mask, diag nullable); ptr: host or
+ * device int64 [B+1], non-decreasing from 0 to N (a device ptr is copied back, which synchronises;
+ * boundaries equal to the previous call's are not uploaded again); loss_out: one device double.
+ * The per-graph sums are accumulated in double for both dtypes over fixed chunks of 2048 scalar
+ * rows split at graph boundaries, then per graph over the chunk partials: the order depends on
+ * neither the grid nor the device.  N = 0 gives loss 0 and launches nothing that indexes; E = 0
+ * with N > 0 is the chain with L = A = 0 (q = 0). */
+int lspcg_graph_spai_loss(lspcg_graph* g, const void* Lvals, const void* Avals, int dtype, double epsilon,
+                          const void* r, const void* mask, const void* diag, const int64_t* ptr, int64_t B, int kind,
+                          double loss_eps, double* loss_out, void* dLvals);
 
 /* ---- one system row-partitioned over ranks (NOT in the reference,
  * whose systems each fit one process -- it replaces no reference interface).  The host driver

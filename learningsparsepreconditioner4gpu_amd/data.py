@@ -3,12 +3,13 @@
 ``GraphSample`` carries the fields of the reference's PyG ``Data`` that the inference
 path reads (``x, edge_index, edge_attr, mask, matrix_values, rsqrt_diag, ptr``);
 ``make_sample`` builds one inference sample of an in-memory matrix through
-``dataset.make_data`` (the restatement of ``neural_cg/data.py:218-336``).
+``dataset.make_data`` (the restatement of ``neural_cg/data.py:218-336``); ``collate`` forms the
+disjoint union of several samples (the reference's PyG ``DataLoader`` batch) for ``loss.spai_loss``.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 import scipy.sparse as sp
@@ -46,6 +47,40 @@ class GraphSample:
         for k, v in self.__dict__.items():
             kw[k] = v.to(device) if isinstance(v, torch.Tensor) and k != "ptr" else v
         return GraphSample(**kw)
+
+
+_PER_ROW_FIELDS = ("x", "edge_attr", "mask", "matrix_values", "diagonal", "inv_diag", "rsqrt_diag", "gt", "residual")
+
+
+def collate(samples: Sequence[GraphSample]) -> GraphSample:
+    """The disjoint union of ``samples`` as one ``GraphSample`` (PyG's ``Batch.from_data_list``
+    for the fields kept here): every per-node and per-edge field concatenated, each sample's node
+    offset added to its ``edge_index``, and ``ptr`` (host int64) holding the node boundaries of
+    the graphs -- a sample that is itself a batch contributes all of its graphs.  A field must be
+    present in every sample or in none."""
+    samples = list(samples)
+    if not samples:
+        raise ValueError("collate needs at least one sample")
+    bs = samples[0].block_size
+    if any(s.block_size != bs for s in samples):
+        raise ValueError("collate: samples of different block_size")
+    kw = {}
+    for name in _PER_ROW_FIELDS:
+        vals = [getattr(s, name) for s in samples]
+        if all(v is None for v in vals):
+            kw[name] = None
+        elif any(v is None for v in vals):
+            raise ValueError(f"collate: field {name!r} is missing from some samples")
+        else:
+            kw[name] = torch.cat(vals)
+    eis, ptr, off = [], [0], 0
+    for s in samples:
+        eis.append(s.edge_index + off)
+        ptr += [off + int(p) for p in s.ptr.tolist()[1:]]
+        off += s.num_nodes
+    scales = {float(s.matrix_scale) for s in samples}
+    return GraphSample(edge_index=torch.cat(eis, dim=1), block_size=bs, ptr=torch.tensor(ptr, dtype=torch.int64),
+                       matrix_scale=scales.pop() if len(scales) == 1 else float("nan"), **kw)
 
 
 def make_sample(A: sp.spmatrix, mask: Optional[np.ndarray] = None, node_features: Optional[np.ndarray] = None,

@@ -318,16 +318,117 @@ def _graph_args(X: torch.Tensor, edge_index: torch.Tensor, A: torch.Tensor, *opt
     return N, bs, x, vals, out, _lib.F32 if X.dtype == torch.float32 else _lib.F64
 
 
+def _wants_grad(*tensors) -> bool:
+    """The autograd path is taken only when gradients are enabled and X or the values ask for one;
+    in every other case the modules below run exactly their no-grad code."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _opt(t):
+    return _ptr(t) if t is not None else None
+
+
+def _spmv(h, code, transpose, vals, x, m):
+    y = torch.empty_like(x)
+    _lib.call("lspcg_graph_spmv", h, _ptr(vals), code, int(transpose), _ptr(x), _opt(m), _ptr(y))
+    return y
+
+
+def _grad_vals(h, code, transpose, gy, x, vals):
+    dv = torch.empty_like(vals)
+    _lib.call("lspcg_graph_spmv_grad_vals", h, code, int(transpose), _ptr(gy), _ptr(x), _ptr(dv))
+    return dv
+
+
+class _GraphSpmvFn(torch.autograd.Function):
+    """``y = m ⊙ (A x)`` (transpose: ``Aᵀ x``) with ``gx = Aᵀ (m ⊙ g)`` (``A (m ⊙ g)``) through
+    lspcg_graph_spmv and ``dA_e = (m⊙g)_I ⊗ x_J`` (``x_I ⊗ (m⊙g)_J``) through
+    lspcg_graph_spmv_grad_vals."""
+
+    @staticmethod
+    def forward(ctx, X, A, edge_index, mask, transpose):
+        N, bs, x, vals, (m,), code = _graph_args(X.detach(), edge_index, A.detach(), mask)
+        ei = edge_index.to(x.device)
+        h = _GRAPHS.get(ei, N, bs)
+        ctx.save_for_backward(x, vals, m)
+        ctx.graph = (ei, N, bs)  # looked up again in backward: the cache may have dropped the handle by then
+        ctx.code, ctx.transpose, ctx.a_like = code, bool(transpose), (A.shape, A.dtype, A.device)
+        return _spmv(h, code, transpose, vals, x, m).reshape(X.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, vals, m = ctx.saved_tensors
+        h = _GRAPHS.get(*ctx.graph)
+        gm = g.reshape(x.shape).contiguous()
+        if m is not None:
+            gm = gm * m.reshape(x.shape)
+        gx = dA = None
+        if ctx.needs_input_grad[0]:
+            gx = _spmv(h, ctx.code, not ctx.transpose, vals, gm, None).reshape(g.shape)
+        if ctx.needs_input_grad[1]:
+            shape, dtype, dev = ctx.a_like
+            dA = _grad_vals(h, ctx.code, ctx.transpose, gm, x, vals).reshape(shape).to(device=dev, dtype=dtype)
+        return gx, dA, None, None, None
+
+
+class _AATPEFn(torch.autograd.Function):
+    """``t = δ m (Lᵀ x) ; y = m (L t) + ε x δ``; ``t`` is saved.  With ``gm = m ⊙ g`` and
+    ``gtm = δ m (Lᵀ gm)``: ``gx = L gtm + ε δ g`` and ``dL_e = gm_I ⊗ t_J + x_I ⊗ gtm_J``."""
+
+    @staticmethod
+    def forward(ctx, x, L, edge_index, mask, diag, epsilon):
+        N, bs, xx, vals, (m, d), code = _graph_args(x.detach(), edge_index, L.detach(), mask, diag)
+        ei = edge_index.to(xx.device)
+        h = _GRAPHS.get(ei, N, bs)
+        t = torch.empty_like(xx)
+        y = torch.empty_like(xx)
+        _lib.call("lspcg_graph_aatpe", h, _ptr(vals), code, float(epsilon), _ptr(xx), _opt(m), _opt(d), _ptr(t),
+                  _ptr(y))
+        ctx.save_for_backward(xx, vals, m, d, t)
+        ctx.graph = (ei, N, bs)
+        ctx.code, ctx.eps, ctx.l_like = code, float(epsilon), (L.shape, L.dtype, L.device)
+        return y.reshape(x.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        xx, vals, m, d, t = ctx.saved_tensors
+        h = _GRAPHS.get(*ctx.graph)
+        g = g.reshape(xx.shape).contiguous()
+        gm = g if m is None else g * m.reshape(xx.shape)
+        gtm = _spmv(h, ctx.code, True, vals, gm, m)
+        if d is not None:
+            gtm = gtm * d.reshape(xx.shape)
+        gx = dL = None
+        if ctx.needs_input_grad[0]:
+            eg = ctx.eps * g
+            gx = _spmv(h, ctx.code, False, vals, gtm, None) + (eg if d is None else eg * d.reshape(xx.shape))
+        if ctx.needs_input_grad[1]:
+            shape, dtype, dev = ctx.l_like
+            dL = _grad_vals(h, ctx.code, False, gm, t, vals) + _grad_vals(h, ctx.code, True, gtm, xx, vals)
+            dL = dL.reshape(shape).to(device=dev, dtype=dtype)
+        return gx, dL, None, None, None, None
+
+
 class GraphSpmv(nn.Module):
     """basic_layers.py:112-142: ``y_i = Σ_j A_ij x_j`` over the blocks of an edge list
-    (``use_transpose``: ``y = Aᵀ x``), then ``y * mask``.  X is [N, b], A is [E, b, b]."""
+    (``use_transpose``: ``y = Aᵀ x``), then ``y * mask``.  X is [N, b], A is [E, b, b].
+    Differentiable with respect to X and A when either requires grad (``_GraphSpmvFn``)."""
 
     def __init__(self, use_transpose: bool = False):
         super().__init__()
         self.transpose = use_transpose
 
-    @torch.no_grad()
     def forward(self, X, edge_index, A, mask=None):
+        if _wants_grad(X, A):
+            if not X.is_cuda:
+                raise _lib.LspcgUnavailable("GraphSpmv / AATPE run on the GPU only (HIP)")
+            return _GraphSpmvFn.apply(X, A, edge_index, mask, self.transpose)
+        return self._forward_no_grad(X, edge_index, A, mask)
+
+    @torch.no_grad()
+    def _forward_no_grad(self, X, edge_index, A, mask=None):
         N, bs, x, vals, (m,), code = _graph_args(X, edge_index, A, mask)
         h = _GRAPHS.get(edge_index.to(x.device), N, bs)
         y = torch.empty_like(x)
@@ -338,7 +439,8 @@ class GraphSpmv(nn.Module):
 
 class AATPE(nn.Module):
     """basic_layers.py:228-261: ``y = ε x + A Aᵀ x`` (``diag``: ``ε diag x + A diag Aᵀ x``), the
-    mask applied after each SpMV -- the ext_spai apply on the GNN's own edge-list output."""
+    mask applied after each SpMV -- the ext_spai apply on the GNN's own edge-list output.
+    Differentiable with respect to x and the values when either requires grad (``_AATPEFn``)."""
 
     def __init__(self, epsilon):
         super().__init__()
@@ -346,8 +448,17 @@ class AATPE(nn.Module):
         self.spmv = GraphSpmv()
         self.spmv_t = GraphSpmv(use_transpose=True)
 
-    @torch.no_grad()
     def forward(self, x, edge_index, boo_values, mask=None, diag=None):
+        if _wants_grad(x, boo_values):
+            if not x.is_cuda:
+                raise _lib.LspcgUnavailable("GraphSpmv / AATPE run on the GPU only (HIP)")
+            if diag is not None:
+                assert tuple(diag.shape) == tuple(x.shape), "diag must have AT_x's shape (basic_layers.py:253)"
+            return _AATPEFn.apply(x, boo_values, edge_index, mask, diag, self.epsilon)
+        return self._forward_no_grad(x, edge_index, boo_values, mask, diag)
+
+    @torch.no_grad()
+    def _forward_no_grad(self, x, edge_index, boo_values, mask=None, diag=None):
         N, bs, xx, vals, (m, d), code = _graph_args(x, edge_index, boo_values, mask, diag)
         if diag is not None:
             assert tuple(diag.shape) == tuple(x.shape), "diag must have AT_x's shape (basic_layers.py:253)"

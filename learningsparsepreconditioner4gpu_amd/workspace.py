@@ -17,7 +17,8 @@ import scipy.sparse as sp
 import torch
 
 from .data import GraphSample
-from .nn import NodeEdgeProcessing, build_gnn, default_gnn_config
+from .loss import create_loss_item, spai_loss
+from .nn import AATPE, NodeEdgeProcessing, build_gnn, default_gnn_config
 from .sparse import DeviceMatrix, assemble
 
 
@@ -111,9 +112,16 @@ def load_checkpoint_weights_only(path: str):
 
 class SimpleInferenceWorkspace:
     def __init__(self, node_features: int, edge_features: int, block_size: int = 1, epsilon: float = 3e-3,
-                 gnn: Optional[dict] = None, seed: Optional[int] = 0, device: Union[str, torch.device] = "cuda"):
+                 gnn: Optional[dict] = None, seed: Optional[int] = 0, device: Union[str, torch.device] = "cuda",
+                 loss_name: str = "RelativeL2Loss_ANorm", loss_params: Optional[dict] = None):
         self.block_size = block_size
         self.epsilon = float(epsilon)
+        # workspace.py:60-67 (config/loss.yaml: batch_less false, RelativeL2Loss_ANorm); built on first
+        # use, so a checkpoint trained with a loss that is not implemented here still serves inference
+        self.loss_name = loss_name
+        self.loss_params = dict(loss_params or {})
+        self._loss_fn = None
+        self.spai_preconditioner = AATPE(self.epsilon)
         cfg = default_gnn_config() if gnn is None else dict(gnn)
         if seed is not None:
             torch.manual_seed(seed)
@@ -138,10 +146,18 @@ class SimpleInferenceWorkspace:
                  block_size=int(hp.get("block_size", 1)), epsilon=float(hp.get("epsilon", 3e-3)),
                  gnn=None if gnn_cfg is None else {k: (dict(v) if hasattr(v, "items") else v)
                                                     for k, v in dict(gnn_cfg).items()},
-                 seed=None, device=device)
+                 seed=None, device=device, **cls._loss_hparams(hp))
         sd = {k[len("gnn."):]: v for k, v in ck["state_dict"].items() if k.startswith("gnn.")}
         ws.gnn.load_state_dict(sd, strict=True)
         return ws
+
+    @staticmethod
+    def _loss_hparams(hp: dict) -> dict:
+        """``loss.name`` / ``loss.params`` of a reference checkpoint (config/loss.yaml), if stored."""
+        loss = hp.get("loss")
+        if not hasattr(loss, "get") or not loss.get("name"):
+            return {}
+        return {"loss_name": str(loss["name"]), "loss_params": dict(loss.get("params") or {})}
 
     def to(self, device) -> "SimpleInferenceWorkspace":
         self.device = torch.device(device)
@@ -156,6 +172,30 @@ class SimpleInferenceWorkspace:
         return boo.reshape(-1, self.block_size, self.block_size)
 
     __call__ = forward
+
+    @property
+    def loss_fn(self):
+        if self._loss_fn is None:
+            self._loss_fn = create_loss_item(self.loss_name, batch_less=False, block_size=self.block_size,
+                                             **self.loss_params)
+        return self._loss_fn
+
+    # ---- workspace.py:96-112 (scaled_workspace.py:98-104 passes diag = batch.inv_diag)
+    def _step_diag(self, batch: GraphSample) -> Optional[torch.Tensor]:
+        return None
+
+    @torch.no_grad()
+    def shared_step(self, batch: GraphSample) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``_shared_step`` without Lightning's logging: ``(boo, loss)`` of a (collated) batch built
+        with ``is_inference=False`` -- the reference's ``Val/Loss`` / ``Test/Loss``.  The two A-norm
+        L2 losses run as the fused ``spai_loss``; ``sqr_out=False`` composes AATPE and the module."""
+        b = batch if batch.x.is_cuda else batch.to(self.device)
+        boo = self.forward(b.x, b.edge_index, b.edge_attr)
+        diag = self._step_diag(b)
+        if self.loss_fn.fused_kind is not None:
+            return boo, spai_loss(b, boo, self.epsilon, diag=diag, kind=self.loss_fn.fused_kind, eps=self.loss_fn.eps)
+        d = self.spai_preconditioner(b.residual, b.edge_index, boo, mask=b.mask, diag=diag)
+        return boo, self.loss_fn(b, d, boo)
 
     def _assemble(self, sample: GraphSample, boo: torch.Tensor, block_output: Optional[bool]) -> DeviceMatrix:
         n = sample.num_nodes * self.block_size
@@ -210,6 +250,10 @@ class SimpleInferenceWorkspace:
 
 class ScaledInferenceWorkspace(SimpleInferenceWorkspace):
     """scaled_workspace.py:199-212: L <- L · diag(rsqrt(diag(A) + 1e-7)), solved with ext_spai_scaled."""
+
+    def _step_diag(self, batch: GraphSample) -> Optional[torch.Tensor]:
+        assert batch.inv_diag is not None, "Relying on batch.inv_diag to maintain stability"
+        return batch.inv_diag
 
     def inference_step(self, sample: GraphSample, time_beg: Optional[float] = None, block_output: Optional[bool] = None,
                        return_scipy: bool = False):
