@@ -285,6 +285,18 @@ int lspcg_gnn_forward(lspcg_gnn* g, int64_t N, int64_t E, const float* x, const 
 /* Which kernels lspcg_gnn_create chose: *f32 = 1 for the fp32-MFMA ones, 0 for the split-f16 GEMMs;
  * *hidden_bound (may be NULL) = the weights' hidden-activation bound that decided it (2^15). */
 int lspcg_gnn_precision(const lspcg_gnn* g, int* f32, double* hidden_bound);
+/* New weights for an existing handle (same layout and count as lspcg_gnn_create; host or device
+ * pointer): re-emits the fragments and re-decides f32 / hidden_bound exactly as lspcg_gnn_create
+ * does, and keeps the workspace and the analysed graph -- an optimizer step costs no re-analysis. */
+int lspcg_gnn_set_weights(lspcg_gnn* g, const float* weights, int64_t nweights);
+/* Gradient of every parameter for grad_out = d loss / d out [E,edge_out]: grad_weights receives
+ * nweights floats in the layout of the weight blob (overwritten, not accumulated).  x, edge_index,
+ * edge_attr as for lspcg_gnn_forward; all device pointers.  Uses the analysed graph (either path),
+ * recomputes the forward in plain fp32 whatever kernels the inference forward runs, keeps its
+ * per-layer states in the handle's workspace ((2L+1) N + (L+4) E rows of 64 B, grown on first use),
+ * and sums in a fixed order without floating-point atomics: the same inputs give the same bits. */
+int lspcg_gnn_backward(lspcg_gnn* g, int64_t N, int64_t E, const float* x, const int64_t* edge_index,
+                       const float* edge_attr, const float* grad_out, float* grad_weights);
 int lspcg_gnn_destroy(lspcg_gnn* g);
 
 /* ---- block SpMV over an edge list (GraphSpmv / AATPE, basic_layers.py:112-142, 228-261) ----

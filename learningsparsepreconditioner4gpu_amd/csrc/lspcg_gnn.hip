@@ -31,18 +31,12 @@
 #include <vector>
 
 #include "lspcg_internal.hpp"
+#include "lspcg_gnn.hpp"
 
 namespace lspcg {
 
-constexpr int H = 16;        // hidden = node_features = edge_features
 constexpr int CE = 256;      // edges per LDS chunk (256 x 16 x 4 B = 16 KiB)
 constexpr int kMaxIn = 32;   // encoder input features supported
-
-using f4 = float __attribute__((ext_vector_type(4)));
-
-// FeedForward(in, out, hidden=16, num_layers=2) parameter block of the packed blob:
-//   [W1 (16 x in) | b1 (16) | W2 (16 x 16) | b2 (16) | W3 (out x 16) | b3 (out)]
-__host__ __device__ constexpr int ff_size(int in, int out) { return H * in + H + H * H + H + out * H + out; }
 
 // Fragment block of one FeedForward (floats): [A1 (S1 x 64) | C1 (64 x 4) | A2 (4 x 64) |
 // C2 (64 x 4) | A3 (4 x 64) | C3 (64 x 4)]
@@ -1121,36 +1115,6 @@ auto featenc = [](int s, int q) { return 4 * s + q; };
 
 }  // namespace
 
-struct lspcg_gnn {
-  lspcg_ctx* ctx = nullptr;
-  lspcg_gnn_desc d{};
-  float* frag = nullptr;  // device fragment blob
-  int64_t o_node_enc = 0, o_edge_enc = 0, o_dec = 0;
-  int64_t o_edge_enc_h = 0;  // split-f16 block of the edge encoder (the first layer's fused copy)
-  bool f32 = false;          // fp32-MFMA kernels (weights past the split-f16 range, or LSPCG_GNN_F32=1)
-  double hidden_bound = 0;   // largest ln_ff_hidden_bound over the layers (what chose f32)
-  std::vector<int64_t> o_layer;  // per layer: [msg | edge | node] fragment block
-  // workspace
-  int64_t capN = -1, capE = -1;
-  float *xa = nullptr, *xb = nullptr, *ecsc = nullptr;
-  int32_t *ptr = nullptr, *cnt = nullptr, *perm = nullptr, *inv = nullptr, *src = nullptr, *dst = nullptr;
-  int* flag = nullptr;
-  void* scan_tmp = nullptr;
-  size_t scan_bytes = 0;
-  // the CSC of the last graph (lspcg_gnn_set_graph): reused while forward gets the same
-  // (edge_index pointer, N, E); gflag != 0: the generic (unsorted / asymmetric) path built it
-  const int64_t* gei = nullptr;
-  int64_t gN = -1, gE = -1;
-  int gflag = 0;
-};
-
-static int64_t gnn_weight_count(const lspcg_gnn_desc& d) {
-  int64_t n = ff_size(d.node_in, H) + ff_size(d.edge_in, H);
-  n += int64_t(d.num_mp_layers) * ((2 * H + ff_size(H, H)) + 2 * (6 * H + ff_size(3 * H, H)));
-  n += ff_size(3 * H, d.edge_out);
-  return n;
-}
-
 static void gnn_free_ws(lspcg_gnn* g) {
   for (void* p : {(void*)g->xa, (void*)g->xb, (void*)g->ecsc, (void*)g->ptr, (void*)g->cnt, (void*)g->perm, (void*)g->inv,
                   (void*)g->src, (void*)g->dst, g->scan_tmp})
@@ -1189,26 +1153,18 @@ static int gnn_reserve(lspcg_gnn* g, int64_t N, int64_t E) {
 
 extern "C" {
 
-int lspcg_gnn_create(lspcg_ctx* ctx, const lspcg_gnn_desc* desc, const float* weights, int64_t nweights,
-                     lspcg_gnn** out) {
-  LSPCG_CHECK(ctx && desc && weights && out, LSPCG_ERR_ARG, "gnn_create: NULL argument");
-  const lspcg_gnn_desc& d = *desc;
-  LSPCG_CHECK(d.hidden == H, LSPCG_ERR_UNSUPPORTED, "gnn_create: hidden must be 16 (gnn.yaml gnn_features)");
-  LSPCG_CHECK(d.mlp_layers == 2, LSPCG_ERR_UNSUPPORTED, "gnn_create: FeedForward num_layers must be 2");
-  LSPCG_CHECK(d.node_in >= 1 && d.node_in <= kMaxIn && d.edge_in >= 1 && d.edge_in <= kMaxIn, LSPCG_ERR_UNSUPPORTED,
-              "gnn_create: node_in / edge_in must be in [1, 32]");
-  LSPCG_CHECK(d.edge_out == 1 || d.edge_out == 4 || d.edge_out == 9, LSPCG_ERR_UNSUPPORTED,
-              "gnn_create: edge_out must be block_size^2 with block_size in {1,2,3}");
-  LSPCG_CHECK(d.num_mp_layers >= 0 && d.num_mp_layers <= 64, LSPCG_ERR_ARG, "gnn_create: bad num_mp_layers");
-  const int64_t need = gnn_weight_count(d);
-  LSPCG_CHECK(nweights == need, LSPCG_ERR_ARG,
-              "gnn_create: weight blob has " + std::to_string(nweights) + " floats, expected " + std::to_string(need));
-  LSPCG_HIP(hipSetDevice(ctx->device));
-  std::unique_ptr<lspcg_gnn> g(new lspcg_gnn());
-  g->ctx = ctx;
-  g->d = d;
+// Host side of lspcg_gnn_create / lspcg_gnn_set_weights: decides f32 / hidden_bound from the
+// weights, emits the fragment blob and uploads it with the weights themselves (the backward works
+// from the unfolded values).  Work queued on the handle's stream may still read the old fragments,
+// so the stream is drained first.
+static int gnn_load_weights(lspcg_gnn* g, const float* weights) {
+  const lspcg_gnn_desc& d = g->d;
+  const int64_t need = g->nweights;
   std::vector<float> w(need);
+  LSPCG_HIP(hipStreamSynchronize(g->ctx->stream));
   LSPCG_HIP(hipMemcpy(w.data(), weights, sizeof(float) * need, hipMemcpyDefault));  // host or device source
+  g->hidden_bound = 0;
+  g->o_layer.clear();
   // precision: the split-f16 GEMMs hold hidden activations below 2^15; weights whose LayerNorm-fed
   // MLPs could exceed that run the exact fp32-MFMA kernels instead (same results to ~1e-7, 1.2x slower)
   {
@@ -1258,6 +1214,7 @@ int lspcg_gnn_create(lspcg_ctx* ctx, const lspcg_gnn_desc* desc, const float* we
     }
   }
   g->o_dec = int64_t(fr.size());
+  g->o_edge_enc_h = 0;
   if (f32) {
     emit_frag(fr, ff_at(w.data() + o, 3 * H, d.edge_out), 12, feat48, nullptr, nullptr);
   } else {
@@ -1265,15 +1222,62 @@ int lspcg_gnn_create(lspcg_ctx* ctx, const lspcg_gnn_desc* desc, const float* we
     g->o_edge_enc_h = int64_t(fr.size());
     if (d.edge_in <= 16) emit_frag_h16(fr, ff_at(enc_w, d.edge_in, H), nullptr, nullptr);
   }
-  LSPCG_HIP(hipMalloc(&g->frag, sizeof(float) * fr.size()));
+  if (int64_t(fr.size()) > g->frag_cap) {  // the fp32 and the split-f16 blobs differ in size
+    (void)hipFree(g->frag);
+    g->frag = nullptr;
+    g->frag_cap = 0;
+    LSPCG_HIP(hipMalloc(&g->frag, sizeof(float) * fr.size()));
+    g->frag_cap = int64_t(fr.size());
+  }
   LSPCG_HIP(hipMemcpy(g->frag, fr.data(), sizeof(float) * fr.size(), hipMemcpyHostToDevice));
+  if (!g->wdev) LSPCG_HIP(hipMalloc(&g->wdev, sizeof(float) * need));
+  LSPCG_HIP(hipMemcpy(g->wdev, w.data(), sizeof(float) * need, hipMemcpyHostToDevice));
+  return LSPCG_OK;
+}
+
+int lspcg_gnn_create(lspcg_ctx* ctx, const lspcg_gnn_desc* desc, const float* weights, int64_t nweights,
+                     lspcg_gnn** out) {
+  LSPCG_CHECK(ctx && desc && weights && out, LSPCG_ERR_ARG, "gnn_create: NULL argument");
+  const lspcg_gnn_desc& d = *desc;
+  LSPCG_CHECK(d.hidden == H, LSPCG_ERR_UNSUPPORTED, "gnn_create: hidden must be 16 (gnn.yaml gnn_features)");
+  LSPCG_CHECK(d.mlp_layers == 2, LSPCG_ERR_UNSUPPORTED, "gnn_create: FeedForward num_layers must be 2");
+  LSPCG_CHECK(d.node_in >= 1 && d.node_in <= kMaxIn && d.edge_in >= 1 && d.edge_in <= kMaxIn, LSPCG_ERR_UNSUPPORTED,
+              "gnn_create: node_in / edge_in must be in [1, 32]");
+  LSPCG_CHECK(d.edge_out == 1 || d.edge_out == 4 || d.edge_out == 9, LSPCG_ERR_UNSUPPORTED,
+              "gnn_create: edge_out must be block_size^2 with block_size in {1,2,3}");
+  LSPCG_CHECK(d.num_mp_layers >= 0 && d.num_mp_layers <= 64, LSPCG_ERR_ARG, "gnn_create: bad num_mp_layers");
+  const int64_t need = gnn_weight_count(d);
+  LSPCG_CHECK(nweights == need, LSPCG_ERR_ARG,
+              "gnn_create: weight blob has " + std::to_string(nweights) + " floats, expected " + std::to_string(need));
+  LSPCG_HIP(hipSetDevice(ctx->device));
+  std::unique_ptr<lspcg_gnn> g(new lspcg_gnn());
+  g->ctx = ctx;
+  g->d = d;
+  g->nweights = need;
+  if (int rc = gnn_load_weights(g.get(), weights)) {
+    (void)hipFree(g->frag);
+    (void)hipFree(g->wdev);
+    return rc;
+  }
   *out = g.release();
   return LSPCG_OK;
 }
 
+int lspcg_gnn_set_weights(lspcg_gnn* g, const float* weights, int64_t nweights) {
+  LSPCG_CHECK(g && weights, LSPCG_ERR_ARG, "gnn_set_weights: NULL argument");
+  LSPCG_CHECK(nweights == g->nweights, LSPCG_ERR_ARG,
+              "gnn_set_weights: weight blob has " + std::to_string(nweights) + " floats, expected " +
+                  std::to_string(g->nweights));
+  LSPCG_HIP(hipSetDevice(g->ctx->device));
+  return gnn_load_weights(g, weights);
+}
+
 // CSC of the edges by destination (the structure analysis of one graph; lspcg_gnn_set_graph)
-static int gnn_build_csc(lspcg_gnn* g, int64_t N, int64_t E, const int64_t* edge_index) {
+}  // extern "C"
+
+int lspcg_gnn_build_csc(lspcg_gnn* g, int64_t N, int64_t E, const int64_t* edge_index) {
   g->gei = nullptr;
+  g->bw.sei = nullptr;  // the backward's by-source order belongs to the previous graph
   if (int rc = gnn_reserve(g, N, E)) return rc;
   g->gei = nullptr;
   g->gN = g->gE = -1;
@@ -1313,12 +1317,14 @@ static int gnn_build_csc(lspcg_gnn* g, int64_t N, int64_t E, const int64_t* edge
   return LSPCG_OK;
 }
 
+extern "C" {
+
 int lspcg_gnn_set_graph(lspcg_gnn* g, int64_t N, int64_t E, const int64_t* edge_index) {
   LSPCG_CHECK(g && (E == 0 || edge_index), LSPCG_ERR_ARG, "gnn_set_graph: NULL argument");
   LSPCG_CHECK(N >= 0 && E >= 0 && N < (int64_t(1) << 31) && E < (int64_t(1) << 31), LSPCG_ERR_ARG,
               "gnn_set_graph: sizes out of range");
   LSPCG_HIP(hipSetDevice(g->ctx->device));
-  return gnn_build_csc(g, N, E, edge_index);
+  return lspcg_gnn_build_csc(g, N, E, edge_index);
 }
 
 int lspcg_gnn_forward(lspcg_gnn* g, int64_t N, int64_t E, const float* x, const int64_t* edge_index,
@@ -1329,7 +1335,7 @@ int lspcg_gnn_forward(lspcg_gnn* g, int64_t N, int64_t E, const float* x, const 
               "gnn_forward: sizes out of range");
   LSPCG_HIP(hipSetDevice(g->ctx->device));
   if (!(g->gei == edge_index && g->gN == N && g->gE == E && N <= g->capN && E <= g->capE))
-    if (int rc = gnn_build_csc(g, N, E, edge_index)) return rc;
+    if (int rc = lspcg_gnn_build_csc(g, N, E, edge_index)) return rc;
   if (E == 0 || N == 0) return LSPCG_OK;
   hipStream_t st = g->ctx->stream;
   const lspcg_gnn_desc& d = g->d;
@@ -1402,7 +1408,9 @@ int lspcg_gnn_destroy(lspcg_gnn* g) {
   if (!g) return LSPCG_OK;
   (void)hipSetDevice(g->ctx->device);
   gnn_free_ws(g);
+  lspcg_gnn_bwd_free(g);
   (void)hipFree(g->frag);
+  (void)hipFree(g->wdev);
   delete g;
   return LSPCG_OK;
 }

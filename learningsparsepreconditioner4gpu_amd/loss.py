@@ -14,8 +14,9 @@ The reference's ``_shared_step`` (``workspace.py:96-112``, ``scaled_workspace.py
   (``AATPE`` of ``nn.py``, or a user's own) and ``sqr_out=False`` is served too.
 
 ``batch`` is a ``data.GraphSample`` (``data.collate`` of several), or any object with
-``residual, edge_index, mask, matrix_values, ptr``.  The GNN's own backward is not native yet:
-a torch-side GNN is trained against these losses through autograd.
+``residual, edge_index, mask, matrix_values, ptr``.  ``boo`` may come from the differentiable
+``NodeEdgeProcessing`` (``nn.py``): ``d loss / d boo`` is then the input of ``lspcg_gnn_backward``
+(``workspace.training_step``).
 """
 from __future__ import annotations
 

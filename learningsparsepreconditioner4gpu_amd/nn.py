@@ -4,8 +4,9 @@ Parameter layout, module names and seeded initialisation follow the reference
 (``neural_cg/nn/gnns.py:9-97``, ``neural_cg/nn/basic_layers.py:73-225``,
 ``neural_cg/utils/weight_init.py``), so ``state_dict()`` keys are the reference's and a
 reference checkpoint's ``gnn.*`` tensors load directly.  The modules here are parameter
-containers; the forward pass is ``lspcg_gnn_forward`` (csrc/lspcg_gnn.hip) -- there is no
-torch compute path.
+containers; the forward pass is ``lspcg_gnn_forward`` (csrc/lspcg_gnn.hip) and, with
+``differentiable = True``, the parameter gradients come from ``lspcg_gnn_backward``
+(csrc/lspcg_gnn_bwd.hip) through ``_GnnFn`` -- there is no torch compute path.
 
 Packed weight blob (fp32, ``pack_weights``), each FeedForward as
 ``[W1 (16 x in) | b1 | W2 (16 x 16) | b2 | W3 (out x 16) | b3]``::
@@ -137,6 +138,7 @@ class NodeEdgeProcessing(nn.Module):
         self._ctx = None
         self._packed_version = None
         self._graph = None  # (key, edge_index tensor) of the structure analysed by lspcg_gnn_set_graph
+        self.differentiable = False  # True: forward builds the parameters' autograd graph (_GnnFn)
 
     @staticmethod
     def _check_supported(nf, ef, *ffs):
@@ -149,32 +151,51 @@ class NodeEdgeProcessing(nn.Module):
                 raise NotImplementedError("the HIP GNN kernel implements GELU hidden / identity output activations")
 
     # ---- packing
-    def pack_weights(self) -> torch.Tensor:
-        parts = []
+    def _packed_params(self):
+        """``[(state_dict key, parameter)]`` in the order of the packed blob."""
+        out = []
 
-        def ff(m: FeedForward):
-            for lin in m.linears():
-                parts.append(lin.weight.detach().reshape(-1))
-                parts.append(lin.bias.detach().reshape(-1))
+        def ff(prefix: str, m: FeedForward):
+            for name, lin in [("lift.0", m.lift[0])] + [(f"body.{i}.0", b[0]) for i, b in enumerate(m.body)] + \
+                    [("proj.0", m.proj[0])]:
+                out.append((f"{prefix}.{name}.weight", lin.weight))
+                out.append((f"{prefix}.{name}.bias", lin.bias))
 
-        def ln(m: FeedForward):
+        def ln(prefix: str, m: FeedForward):
             if not isinstance(m.pre_norm, nn.LayerNorm):
                 raise NotImplementedError("MPLayer MLPs must use pre_norm 'layer' (config/gnn.yaml)")
-            parts.append(m.pre_norm.weight.detach().reshape(-1))
-            parts.append(m.pre_norm.bias.detach().reshape(-1))
+            out.append((f"{prefix}.pre_norm.weight", m.pre_norm.weight))
+            out.append((f"{prefix}.pre_norm.bias", m.pre_norm.bias))
 
-        for enc in (self.node_enc, self.edge_enc):
+        for name, enc in (("node_enc", self.node_enc), ("edge_enc", self.edge_enc)):
             if not isinstance(enc.pre_norm, nn.Identity):
                 raise NotImplementedError("encoders must use pre_norm 'none' (config/gnn.yaml)")
-            ff(enc)
-        for mp in self.mp_layers:
-            for sub in (mp.node_mlp, mp.edge_mlp, mp.msg_mlp):
-                ln(sub)
-                ff(sub)
+            ff(name, enc)
+        for i, mp in enumerate(self.mp_layers):
+            for name, sub in (("node_mlp", mp.node_mlp), ("edge_mlp", mp.edge_mlp), ("msg_mlp", mp.msg_mlp)):
+                ln(f"mp_layers.{i}.{name}", sub)
+                ff(f"mp_layers.{i}.{name}", sub)
         if not isinstance(self.edge_dec.pre_norm, nn.Identity):
             raise NotImplementedError("edge decoder must use pre_norm 'none' (config/gnn.yaml)")
-        ff(self.edge_dec)
-        return torch.cat([p.float().cpu() for p in parts]).contiguous()
+        ff("edge_dec", self.edge_dec)
+        return out
+
+    def pack_weights(self) -> torch.Tensor:
+        """The fp32 weight blob on the host: one ``cat`` on the parameters' device, one copy."""
+        parts = [p.detach().reshape(-1).float() for _, p in self._packed_params()]
+        return torch.cat(parts).cpu().contiguous()
+
+    def unpack_grads(self, blob: torch.Tensor) -> dict:
+        """The inverse of ``pack_weights``: ``{state_dict key: tensor}`` views of a blob in its layout
+        (the gradient blob of ``lspcg_gnn_backward``, or the weights themselves)."""
+        out, o = {}, 0
+        flat = blob.reshape(-1)
+        for key, p in self._packed_params():
+            n = p.numel()
+            out[key] = flat[o:o + n].reshape(p.shape)
+            o += n
+        assert o == flat.numel(), (o, flat.numel())
+        return out
 
     def _version(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
@@ -183,9 +204,15 @@ class NodeEdgeProcessing(nn.Module):
         ctx = Context.get(device)
         if self._handle is not None and self._ctx is ctx and self._packed_version == self._version():
             return
+        blob = self.pack_weights()
+        if self._handle is not None and self._ctx is ctx:
+            # only the values changed (an optimizer step): the handle, its workspace and the analysed
+            # graph stay
+            _lib.call("lspcg_gnn_set_weights", self._handle, blob.data_ptr(), blob.numel())
+            self._packed_version = self._version()
+            return
         self._free()
         self._graph = None
-        blob = self.pack_weights()
         desc = _lib.lspcg_gnn_desc(node_in=self.node_in_features, edge_in=self.edge_in_features, hidden=self.hidden,
                                    mlp_layers=2, num_mp_layers=self.num_mp_layers,
                                    edge_out=self.edge_out_features, node_residual=int(self.node_residual),
@@ -226,10 +253,24 @@ class NodeEdgeProcessing(nn.Module):
         counter does not see (.data, DLPack / CuPy views); also frees the held tensor."""
         self._graph = None
 
-    @torch.no_grad()
     def forward(self, node_attr: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Tensor):
         """Returns ``(None, edge_out [E, b*b])``; the reference's node output is the identity
-        node decoder of the final node state, which the hot path discards (workspace.py:93)."""
+        node decoder of the final node state, which the hot path discards (workspace.py:93).
+        With ``differentiable`` set, gradients enabled and a parameter that requires grad, the
+        output carries the parameters' autograd graph (``_GnnFn``); its bits are the same."""
+        if self.differentiable and torch.is_grad_enabled():
+            if node_attr.requires_grad or edge_attr.requires_grad:
+                raise NotImplementedError("gradients with respect to node_attr / edge_attr are not implemented")
+            params = [p for _, p in self._packed_params()]
+            if any(p.requires_grad for p in params):
+                if not node_attr.is_cuda:
+                    raise _lib.LspcgUnavailable("NodeEdgeProcessing.forward runs on the GPU only (HIP)")
+                return None, _GnnFn.apply(self, node_attr, edge_index, edge_attr, *params)
+        return None, self._forward_no_grad(node_attr, edge_index, edge_attr)[3]
+
+    @torch.no_grad()
+    def _forward_no_grad(self, node_attr: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Tensor):
+        """``(x, edge_index, edge_attr, out)``: the tensors the kernels saw, and the output."""
         if not node_attr.is_cuda:
             raise _lib.LspcgUnavailable("NodeEdgeProcessing.forward runs on the GPU only (HIP)")
         dev = node_attr.device
@@ -241,6 +282,11 @@ class NodeEdgeProcessing(nn.Module):
         assert x.shape[1] == self.node_in_features, (x.shape, self.node_in_features)
         assert ea.shape == (E, self.edge_in_features), (ea.shape, self.edge_in_features)
         out = torch.empty(E, self.edge_out_features, dtype=torch.float32, device=dev)
+        self._set_graph(ei, N, E)
+        _lib.call("lspcg_gnn_forward", self._handle, N, E, _ptr(x), _ptr(ei), _ptr(ea), _ptr(out))
+        return x, ei, ea, out
+
+    def _set_graph(self, ei: torch.Tensor, N: int, E: int):
         # the graph's CSC is analysed once per edge_index (the tensor is held, so its address cannot
         # be reused by another one while cached; an in-place torch op bumps its version -- writes
         # that bypass the version counter, through .data, DLPack or CuPy views, must be followed by
@@ -249,18 +295,57 @@ class NodeEdgeProcessing(nn.Module):
         if self._graph is None or self._graph[0] != key or self._graph[1].data_ptr() != ei.data_ptr():
             _lib.call("lspcg_gnn_set_graph", self._handle, N, E, _ptr(ei))
             self._graph = (key, ei)
-        _lib.call("lspcg_gnn_forward", self._handle, N, E, _ptr(x), _ptr(ei), _ptr(ea), _ptr(out))
-        return None, out
+
+    def _backward(self, x, ei, ea, grad_out: torch.Tensor) -> torch.Tensor:
+        """The gradient blob (``pack_weights`` layout, fp32, on the device) for ``d loss / d out``."""
+        self._ensure_handle(x.device)
+        N, E = x.shape[0], ei.shape[1]
+        self._set_graph(ei, N, E)
+        go = grad_out.to(device=x.device, dtype=torch.float32).contiguous()
+        assert go.shape == (E, self.edge_out_features), (tuple(go.shape), E, self.edge_out_features)
+        gw = torch.empty(sum(p.numel() for _, p in self._packed_params()), dtype=torch.float32, device=x.device)
+        _lib.call("lspcg_gnn_backward", self._handle, N, E, _ptr(x), _ptr(ei), _ptr(ea), _ptr(go), _ptr(gw))
+        return gw
 
 
-def build_gnn(node_in: int, edge_in: int, block_size: int, seed: Optional[int] = 0, **over) -> NodeEdgeProcessing:
-    """Seeded construction with the reference's config (workspace.py:70-76, config/gnn.yaml)."""
+class _GnnFn(torch.autograd.Function):
+    """``out = lspcg_gnn_forward(...)`` (the no-grad path's own call, so the same bits); backward
+    runs ``lspcg_gnn_backward`` and hands every parameter its slice of the gradient blob."""
+
+    @staticmethod
+    def forward(ctx, gnn, node_attr, edge_index, edge_attr, *params):
+        x, ei, ea, out = gnn._forward_no_grad(node_attr.detach(), edge_index, edge_attr.detach())
+        ctx.gnn = gnn
+        ctx.save_for_backward(x, ei, ea)
+        ctx.version = gnn._version()
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gnn = ctx.gnn
+        x, ei, ea = ctx.saved_tensors
+        if gnn._version() != ctx.version:
+            raise RuntimeError("a GNN parameter was modified in place between forward and backward")
+        grads = gnn.unpack_grads(gnn._backward(x, ei, ea, g))
+        outs = []
+        for (key, p), need in zip(gnn._packed_params(), ctx.needs_input_grad[4:]):
+            outs.append(grads[key].to(device=p.device, dtype=p.dtype) if need else None)
+        return (None, None, None, None, *outs)
+
+
+def build_gnn(node_in: int, edge_in: int, block_size: int, seed: Optional[int] = 0, differentiable: bool = False,
+              **over) -> NodeEdgeProcessing:
+    """Seeded construction with the reference's config (workspace.py:70-76, config/gnn.yaml).
+    ``differentiable=True``: the forward is differentiable with respect to the parameters."""
     cfg = default_gnn_config()
     cfg.update(over)
     if seed is not None:
         torch.manual_seed(seed)
-    return NodeEdgeProcessing(node_in_features=node_in, node_out_features=None, edge_in_features=edge_in,
-                              edge_out_features=block_size * block_size, **cfg)
+    gnn = NodeEdgeProcessing(node_in_features=node_in, node_out_features=None, edge_in_features=edge_in,
+                             edge_out_features=block_size * block_size, **cfg)
+    gnn.differentiable = bool(differentiable)
+    return gnn
 
 
 # ---------------------------------------------------------------------------

@@ -197,6 +197,26 @@ class SimpleInferenceWorkspace:
         d = self.spai_preconditioner(b.residual, b.edge_index, boo, mask=b.mask, diag=diag)
         return boo, self.loss_fn(b, d, boo)
 
+    # ---- workspace.py:96-112, 178-180 (training_step = _shared_step with gradients)
+    def parameters(self):
+        """The GNN's parameters (``torch.optim.Adam(ws.parameters())``)."""
+        return self.gnn.parameters()
+
+    def training_step(self, batch: GraphSample) -> torch.Tensor:
+        """The reference's ``training_step`` without Lightning: the loss of a (collated) batch built
+        with ``is_inference=False``, differentiable with respect to the GNN's parameters --
+        ``lspcg_gnn_forward``, the fused ``spai_loss`` (``sqr_out=False``: AATPE and the module) and,
+        on ``loss.backward()``, ``lspcg_gnn_backward``.  Sets ``gnn.differentiable``."""
+        self.gnn.differentiable = True
+        b = batch if batch.x.is_cuda else batch.to(self.device)
+        with torch.enable_grad():
+            boo = self.forward(b.x, b.edge_index, b.edge_attr)
+            diag = self._step_diag(b)
+            if self.loss_fn.fused_kind is not None:
+                return spai_loss(b, boo, self.epsilon, diag=diag, kind=self.loss_fn.fused_kind, eps=self.loss_fn.eps)
+            d = self.spai_preconditioner(b.residual, b.edge_index, boo, mask=b.mask, diag=diag)
+            return self.loss_fn(b, d, boo)
+
     def _assemble(self, sample: GraphSample, boo: torch.Tensor, block_output: Optional[bool]) -> DeviceMatrix:
         n = sample.num_nodes * self.block_size
         bo = (self.block_size > 1) if block_output is None else block_output
