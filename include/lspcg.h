@@ -19,6 +19,8 @@
  *   neural_cg/nn/basic_layers.py:112-142 GraphSpmv.forward        -> lspcg_graph_spmv
  *   neural_cg/nn/basic_layers.py:228-261 AATPE.forward            -> lspcg_graph_aatpe
  *       (edge lists prepared once by lspcg_graph_create)
+ *   neural_cg/utils/optim.py:4-12 create_optimizer (torch.optim.SGD / Adam / AdamW) + Lightning's
+ *       gradient_clip_val (clip_grad_norm_, config/trainer.yaml)  -> lspcg_optim_step
  *
  * Conventions: plain pointers and sizes only.  Vector arguments of compute calls are
  * DEVICE pointers; matrix/weight uploads accept host or device pointers.  All work is
@@ -346,6 +348,35 @@ int lspcg_graph_spmv_grad_vals(lspcg_graph* g, int dtype, int transpose, const v
 int lspcg_graph_spai_loss(lspcg_graph* g, const void* Lvals, const void* Avals, int dtype, double epsilon,
                           const void* r, const void* mask, const void* diag, const int64_t* ptr, int64_t B, int kind,
                           double loss_eps, double* loss_out, void* dLvals);
+
+/* ---- gradient clipping + optimizer step over a flat fp32 blob (neural_cg/utils/optim.py
+ * create_optimizer: torch.optim.SGD / Adam / AdamW; Lightning's gradient_clip_val =
+ * torch.nn.utils.clip_grad_norm_, config/trainer.yaml) ----
+ * One launch of one workgroup on the context's stream; no state is kept and nothing synchronises.
+ * All pointers are DEVICE pointers.  With g = coef * (float(grad_scale) * grad) and
+ * coef = min(1, clip_norm / (‖float(grad_scale) * grad‖ + 1e-6)) (1 when clip_norm <= 0), the update
+ * is torch.optim's non-capturable single-tensor one (no amsgrad / maximize / nesterov / dampening):
+ *   ADAMW  w *= 1 - lr wd ; m += (1-β1)(g - m) ; v = β2 v + (1-β2) g² ;
+ *          w -= lr/(1-β1^step) · m / (sqrt(v)/sqrt(1-β2^step) + eps)
+ *   ADAM   the same with g += wd w in place of the decoupled decay
+ *   SGD    g += wd w ; momentum != 0: m = g (step 1) or momentum m + g, g = m ; w -= lr g
+ * evaluated in double and rounded once per stored fp32 value.  m, v: n floats each, zero before
+ * step 1; v may be NULL for SGD, m too for SGD without momentum.  stats (4 doubles, may be NULL)
+ * receives ‖float(grad_scale) * grad‖ before clipping, coef, ‖w‖ before and ‖w‖ after the step.
+ * The norms are fixed-shape sums in double without floating-point atomics: the same inputs give the
+ * same bits, whatever the pointers' alignment.  Non-finite gradients propagate as in torch.  n = 0
+ * touches no array and still writes stats.  Sized for parameter counts up to a few 10^5. */
+#define LSPCG_OPT_SGD 0
+#define LSPCG_OPT_ADAM 1
+#define LSPCG_OPT_ADAMW 2
+typedef struct {
+  int kind; /* LSPCG_OPT_SGD / _ADAM / _ADAMW */
+  double beta1, beta2, eps, weight_decay, momentum;
+  double clip_norm;  /* <= 0: no clipping */
+  double grad_scale; /* multiplies grad first (1 / accumulate_grad_batches) */
+} lspcg_optim_desc;
+int lspcg_optim_step(lspcg_ctx* ctx, const lspcg_optim_desc* desc, int64_t n, int64_t step, double lr, float* w,
+                     const float* grad, float* m, float* v, double* stats);
 
 /* ---- one system row-partitioned over ranks (NOT in the reference,
  * whose systems each fit one process -- it replaces no reference interface).  The host driver

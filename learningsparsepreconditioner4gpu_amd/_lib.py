@@ -31,6 +31,13 @@ class lspcg_gnn_desc(C.Structure):
                                       "edge_out", "node_residual", "edge_residual")]
 
 
+class lspcg_optim_desc(C.Structure):
+    _fields_ = [("kind", C.c_int)] + [(n, C.c_double) for n in ("beta1", "beta2", "eps", "weight_decay", "momentum",
+                                                                "clip_norm", "grad_scale")]
+
+
+OPT_KIND = {"sgd": 0, "adam": 1, "adamw": 2}
+
 # name -> (restype, argtypes); the list IS the exported ABI (tests check it against include/lspcg.h)
 SIGNATURES = {
     "lspcg_last_error": (C.c_char_p, []),
@@ -88,6 +95,8 @@ SIGNATURES = {
     "lspcg_graph_spmv_grad_vals": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
     "lspcg_graph_spai_loss": (C.c_int, [vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp, C.c_int64, C.c_int,
                                         C.c_double, vp, vp]),
+    "lspcg_optim_step": (C.c_int, [vp, C.POINTER(lspcg_optim_desc), C.c_int64, C.c_int64, C.c_double, vp, vp, vp, vp,
+                                   vp]),
     "lspcg_part_create": (C.c_int, [vp, vp, vp, vp, C.c_int64, vp, C.c_int64, pp]),
     "lspcg_part_destroy": (C.c_int, [vp]),
     "lspcg_part_pack": (C.c_int, [vp, vp, vp]),

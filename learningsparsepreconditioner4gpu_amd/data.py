@@ -85,8 +85,10 @@ def collate(samples: Sequence[GraphSample]) -> GraphSample:
 
 def make_sample(A: sp.spmatrix, mask: Optional[np.ndarray] = None, node_features: Optional[np.ndarray] = None,
                 block_size: int = 1, use_mask_as_node_feature: bool = True,
-                use_edge_features_as_node_feature: str = "disable", normalize_matrix="mean") -> GraphSample:
-    """make_data (data.py:218-336) for an inference sample of an in-memory matrix ``A``: the
+                use_edge_features_as_node_feature: str = "disable", normalize_matrix="mean",
+                is_inference: bool = True) -> GraphSample:
+    """make_data (data.py:218-336) for a sample of an in-memory matrix ``A`` (``is_inference=False``:
+    a training sample with a random right-hand side drawn from torch's global generator): the
     block COO view of A (``FolderDataset.load``'s layout, data.py:471-572) fed to
     ``dataset.make_data`` -- the one restatement of make_data, golden-checked for every option."""
     from .dataset import RawData, make_data
@@ -102,4 +104,4 @@ def make_sample(A: sp.spmatrix, mask: Optional[np.ndarray] = None, node_features
     return make_data(raw, use_matrix_as_edge_feature=True, use_mask_as_node_feature=use_mask_as_node_feature,
                      use_node_features_as_edge_feature=False,
                      use_edge_features_as_node_feature=use_edge_features_as_node_feature, use_random_rhs=True,
-                     normalize_matrix=normalize_matrix, is_inference=True)
+                     normalize_matrix=normalize_matrix, is_inference=is_inference)

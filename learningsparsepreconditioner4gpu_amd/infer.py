@@ -23,6 +23,7 @@ torchrun (``distributed.run_sharded``) with a single all-gather at the end.
 from __future__ import annotations
 
 import argparse
+import itertools
 import math
 import os
 from dataclasses import dataclass, field
@@ -33,7 +34,8 @@ import numpy as np
 import torch
 
 from . import problems as P
-from .data import GraphSample, make_sample
+from .data import GraphSample
+from .data import make_sample as _make_sample
 from .distributed import SolveRecord, run_sharded, run_sharded_batched, run_sharded_concurrent
 from .validate import get_cg_iter_time, get_pcg_iter_time, get_pcg_iter_time_batch, get_pcg_scaled_iter_time
 from .workspace import ScaledInferenceWorkspace, SimpleInferenceWorkspace
@@ -95,8 +97,20 @@ class Timestat:
                   f"{np.mean(st.all_prec_time) * 1e3:.2f} ms, {np.mean(st.all_iteration):.4f} it/sample")
 
 
-def synthetic_dataset(name: str) -> List[GraphSample]:
-    """Stand-in datasets; the reference's generated/ folders are absent."""
+def synthetic_dataset(name: str, is_inference: bool = True) -> List[GraphSample]:
+    """Stand-in datasets; the reference's generated/ folders are absent.
+    ``is_inference=False`` builds training samples (train.py): each with a random right-hand side,
+    drawn after ``torch.manual_seed(its index)`` so that the set is the same every time."""
+    index = itertools.count()
+
+    def make_sample(*a, **kw):
+        if not is_inference:
+            torch.manual_seed(next(index))
+        return _make_sample(*a, is_inference=is_inference, **kw)
+
+    if name == "poisson_tiny8":  # 8 Poisson-2D grids of 36-144 unknowns: the smallest set a training run fits
+        sizes = [(6, 6), (7, 8), (8, 7), (9, 9), (10, 8), (11, 10), (12, 11), (12, 12)]
+        return [make_sample(*P.poisson2d_grid(nx, ny, seed=k)[:2]) for k, (nx, ny) in enumerate(sizes)]
     if name == "heat_batch8":  # C5: 8 heat-tet systems, 400-32000 vertices, seeds 0-7
         rng = np.random.default_rng(0)
         out = []
@@ -354,7 +368,8 @@ def main(argv=None):
     ap.add_argument("--rhs-seed", type=int, default=0, help="rhs=random: sample i draws from default_rng(seed + i)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workspace", default="simple", choices=["simple", "scaled"])
-    ap.add_argument("--pretrained", default="")
+    ap.add_argument("--pretrained", "--checkpoint", dest="pretrained", default="",
+                    help="a checkpoint of the reference (Lightning) or of train.py")
     ap.add_argument("--epsilon", type=float, default=3e-3)
     ap.add_argument("--out-dir", default="output")
     ap.add_argument("--infer-prefix", default="")

@@ -45,29 +45,36 @@ def _graph_ptrs(batch, batch_less: bool) -> List[int]:
     return [int(v) for v in torch.as_tensor(batch.ptr).detach().cpu().tolist()]
 
 
+def _spai_loss_launch(boo, r, edge_index, A, mask, diag, ptr, epsilon, kind, eps, want_grad):
+    """One ``lspcg_graph_spai_loss`` call: ``(loss as a device double, d loss / d boo or None)``."""
+    N = r.shape[0]
+    bs = r.shape[1] if r.ndim == 2 else 1
+    E = edge_index.shape[1]
+    dt, dev = boo.dtype, r.device
+    code = _lib.F32 if dt == torch.float32 else _lib.F64
+    cast = lambda t: None if t is None else t.detach().to(device=dev, dtype=dt).contiguous()
+    Lv, Av, rr, m, d = cast(boo), cast(A), cast(r), cast(mask), cast(diag)
+    assert Lv.numel() == E * bs * bs and Av.numel() == E * bs * bs, (tuple(Lv.shape), tuple(Av.shape), E, bs)
+    for o in (m, d):
+        assert o is None or o.numel() == N * bs, (tuple(o.shape), N, bs)
+    h = _GRAPHS.get(edge_index.to(dev), N, bs)
+    hp = torch.as_tensor(ptr, dtype=torch.int64).cpu().contiguous()
+    out = torch.empty((), dtype=torch.float64, device=dev)
+    dL = torch.empty_like(Lv) if want_grad else None
+    _lib.call("lspcg_graph_spai_loss", h, _ptr(Lv), _ptr(Av), code, float(epsilon), _ptr(rr), _opt(m), _opt(d),
+              C.c_void_p(hp.data_ptr()), int(hp.numel() - 1), int(kind), float(eps), _ptr(out), _opt(dL))
+    return out, dL
+
+
 class _SpaiLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, boo, r, edge_index, A, mask, diag, ptr, epsilon, kind, eps):
-        N = r.shape[0]
-        bs = r.shape[1] if r.ndim == 2 else 1
-        E = edge_index.shape[1]
-        dt, dev = boo.dtype, r.device
-        code = _lib.F32 if dt == torch.float32 else _lib.F64
-        cast = lambda t: None if t is None else t.detach().to(device=dev, dtype=dt).contiguous()
-        Lv, Av, rr, m, d = cast(boo), cast(A), cast(r), cast(mask), cast(diag)
-        assert Lv.numel() == E * bs * bs and Av.numel() == E * bs * bs, (tuple(Lv.shape), tuple(Av.shape), E, bs)
-        for o in (m, d):
-            assert o is None or o.numel() == N * bs, (tuple(o.shape), N, bs)
-        h = _GRAPHS.get(edge_index.to(dev), N, bs)
-        hp = torch.as_tensor(ptr, dtype=torch.int64).cpu().contiguous()
-        out = torch.empty((), dtype=torch.float64, device=dev)
-        dL = torch.empty_like(Lv) if ctx.needs_input_grad[0] else None
-        _lib.call("lspcg_graph_spai_loss", h, _ptr(Lv), _ptr(Av), code, float(epsilon), _ptr(rr), _opt(m), _opt(d),
-                  C.c_void_p(hp.data_ptr()), int(hp.numel() - 1), int(kind), float(eps), _ptr(out), _opt(dL))
+        out, dL = _spai_loss_launch(boo, r, edge_index, A, mask, diag, ptr, epsilon, kind, eps,
+                                    ctx.needs_input_grad[0])
         if dL is not None:
             ctx.save_for_backward(dL)
             ctx.like = (boo.shape, boo.device)
-        return out.to(dt)
+        return out.to(boo.dtype)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -77,21 +84,37 @@ class _SpaiLossFn(torch.autograd.Function):
         return ((g.to(dL.dtype) * dL).reshape(shape).to(dev),) + (None,) * 9
 
 
+def _check_spai_args(batch, boo, kind):
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {sorted(KINDS)}, got {kind!r}")
+    if batch.residual is None:
+        raise ValueError("the batch has no residual (build the samples with is_inference=False)")
+    if not batch.residual.is_cuda:
+        raise _lib.LspcgUnavailable("spai_loss runs on the GPU only (HIP)")
+    if boo.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"unsupported dtype {boo.dtype}")
+
+
+def spai_loss_and_grad(batch, boo: torch.Tensor, epsilon: float, diag: Optional[torch.Tensor] = None,
+                       kind: str = "relative", eps: float = 1e-6):
+    """``spai_loss`` without autograd: ``(loss, d loss / d boo)`` straight from the one launch
+    sequence -- the loss bits of ``spai_loss`` and the gradient bits its ``backward`` hands out for
+    an upstream gradient of 1.  ``boo`` is treated as a constant; the loss stays on the device."""
+    _check_spai_args(batch, boo, kind)
+    with torch.no_grad():
+        out, dL = _spai_loss_launch(boo, batch.residual, batch.edge_index, batch.matrix_values, batch.mask, diag,
+                                    _graph_ptrs(batch, False), float(epsilon), KINDS[kind], float(eps), True)
+        return out.to(boo.dtype), dL.reshape(boo.shape)
+
+
 def spai_loss(batch, boo: torch.Tensor, epsilon: float, diag: Optional[torch.Tensor] = None, kind: str = "relative",
               eps: float = 1e-6) -> torch.Tensor:
     """``loss_fn(batch, AATPE(epsilon)(batch.residual, batch.edge_index, boo, batch.mask, diag), boo)``
     for ``RelativeL2Loss_ANorm`` (``kind="relative"``, ``sqr_out=True``) or ``L2Loss_ANorm``
     (``kind="mse"``), as a scalar tensor of ``boo``'s dtype.  When ``boo`` requires grad, the same
     launch sequence also leaves ``d loss / d boo``, which ``backward`` hands out."""
-    if kind not in KINDS:
-        raise ValueError(f"kind must be one of {sorted(KINDS)}, got {kind!r}")
+    _check_spai_args(batch, boo, kind)
     r = batch.residual
-    if r is None:
-        raise ValueError("the batch has no residual (build the samples with is_inference=False)")
-    if not r.is_cuda:
-        raise _lib.LspcgUnavailable("spai_loss runs on the GPU only (HIP)")
-    if boo.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"unsupported dtype {boo.dtype}")
     return _SpaiLossFn.apply(boo, r, batch.edge_index, batch.matrix_values, batch.mask, diag,
                              _graph_ptrs(batch, False), float(epsilon), KINDS[kind], float(eps))
 

@@ -137,6 +137,7 @@ class NodeEdgeProcessing(nn.Module):
         self._handle = None
         self._ctx = None
         self._packed_version = None
+        self.flat = None  # the fp32 device blob all packed parameters are views of (flatten_parameters)
         self._graph = None  # (key, edge_index tensor) of the structure analysed by lspcg_gnn_set_graph
         self.differentiable = False  # True: forward builds the parameters' autograd graph (_GnnFn)
 
@@ -181,9 +182,56 @@ class NodeEdgeProcessing(nn.Module):
         return out
 
     def pack_weights(self) -> torch.Tensor:
-        """The fp32 weight blob on the host: one ``cat`` on the parameters' device, one copy."""
+        """The fp32 weight blob on the host: one ``cat`` on the parameters' device, one copy.
+        After ``flatten_parameters`` it is ``self.flat`` itself (on the device, no copy)."""
+        if self.is_flat():
+            return self.flat
         parts = [p.detach().reshape(-1).float() for _, p in self._packed_params()]
         return torch.cat(parts).cpu().contiguous()
+
+    # ---- flat parameters (opt-in; the native optimizer writes them in place)
+    def flatten_parameters(self, device="cuda") -> torch.Tensor:
+        """Move the module to ``device`` and re-point every packed parameter's ``.data`` at a view of
+        ONE fp32 device tensor in blob order (``self.flat``, returned).  From then on ``pack_weights``
+        is free, ``lspcg_gnn_set_weights`` reads the device blob, ``lspcg_optim_step`` updates the
+        live parameters in place and ``state_dict()`` is always current.  The values keep their bits.
+        Anything that re-allocates a parameter (``.to(other device)``, ``.double()``) ends the flat
+        state (``is_flat()`` turns False and the module packs as before)."""
+        self.to(torch.device(device))
+        packed = self._packed_params()
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in packed]).contiguous()
+        o = 0
+        for _, p in packed:
+            n = p.numel()
+            p.data = flat[o:o + n].view(p.shape)
+            o += n
+        self.flat = flat
+        self._packed_version = None
+        return flat
+
+    def is_flat(self) -> bool:
+        """Every packed parameter still is its view of ``self.flat``."""
+        flat = self.flat
+        if flat is None:
+            return False
+        o, base = 0, flat.data_ptr()
+        for _, p in self._packed_params():
+            if p.dtype != torch.float32 or p.data_ptr() != base + 4 * o:
+                return False
+            o += p.numel()
+        return o == flat.numel()
+
+    def weights_updated_in_place(self):
+        """``self.flat`` was written behind torch's version counters (``lspcg_optim_step``): hand the
+        new values to the handle now (``lspcg_gnn_set_weights`` from the device blob; the workspace
+        and the analysed graph stay) and mark them packed, so the next forward uploads nothing."""
+        assert self.is_flat(), "weights_updated_in_place needs flatten_parameters()"
+        if self._handle is None or self._ctx is not Context.get(self.flat.device):
+            self._packed_version = None
+            self._ensure_handle(self.flat.device)
+            return
+        _lib.call("lspcg_gnn_set_weights", self._handle, _ptr(self.flat), self.flat.numel())
+        self._packed_version = self._version()
 
     def unpack_grads(self, blob: torch.Tensor) -> dict:
         """The inverse of ``pack_weights``: ``{state_dict key: tensor}`` views of a blob in its layout

@@ -17,7 +17,7 @@ import scipy.sparse as sp
 import torch
 
 from .data import GraphSample
-from .loss import create_loss_item, spai_loss
+from .loss import create_loss_item, spai_loss, spai_loss_and_grad
 from .nn import AATPE, NodeEdgeProcessing, build_gnn, default_gnn_config
 from .sparse import DeviceMatrix, assemble
 
@@ -129,6 +129,10 @@ class SimpleInferenceWorkspace:
                                       edge_in_features=edge_features, edge_out_features=block_size * block_size,
                                       **cfg)
         self.device = torch.device(device)
+        self.node_features, self.edge_features, self.gnn_config = int(node_features), int(edge_features), cfg
+        self.history: list = []  # one dict of metrics per epoch of fit()
+        self.last_checkpoint: Optional[str] = None
+        self.last_grad_blob: Optional[torch.Tensor] = None  # what fit_step handed to the optimizer last
 
     # ---- checkpoints (workspace.py:52 save_hyperparameters; infer.py:237 load_from_checkpoint)
     @classmethod
@@ -216,6 +220,44 @@ class SimpleInferenceWorkspace:
                 return spai_loss(b, boo, self.epsilon, diag=diag, kind=self.loss_fn.fused_kind, eps=self.loss_fn.eps)
             d = self.spai_preconditioner(b.residual, b.edge_index, boo, mask=b.mask, diag=diag)
             return self.loss_fn(b, d, boo)
+
+    # ---- training without autograd (train.py holds the loop)
+    def fit_step(self, batch: GraphSample, optimizer, lr: Optional[float] = None) -> torch.Tensor:
+        """One training step with no autograd graph: ``lspcg_gnn_forward``, the fused loss with its
+        ``d loss / d boo`` (``spai_loss_and_grad``; ``sqr_out=False``: ``torch.autograd.grad`` through
+        AATPE and the module), ``lspcg_gnn_backward`` and ``optimizer.step`` (``optim.NativeOptimizer``:
+        accumulation if configured, ``lspcg_optim_step``, ``lspcg_gnn_set_weights``).  The loss and the
+        gradient blob have ``training_step`` / ``backward``'s bits.  Returns the loss as a device
+        scalar; nothing is read back."""
+        b = batch if batch.x.is_cuda else batch.to(self.device)
+        x, ei, ea, out = self.gnn._forward_no_grad(b.x, b.edge_index, b.edge_attr)
+        boo = out.reshape(-1, self.block_size, self.block_size)
+        diag = self._step_diag(b)
+        if self.loss_fn.fused_kind is not None:
+            loss, dL = spai_loss_and_grad(b, boo, self.epsilon, diag=diag, kind=self.loss_fn.fused_kind,
+                                          eps=self.loss_fn.eps)
+        else:
+            leaf = boo.detach().requires_grad_(True)
+            with torch.enable_grad():
+                d = self.spai_preconditioner(b.residual, b.edge_index, leaf, mask=b.mask, diag=diag)
+                loss = self.loss_fn(b, d, leaf)
+            (dL,) = torch.autograd.grad(loss, leaf)
+            loss = loss.detach()
+        self.last_grad_blob = self.gnn._backward(x, ei, ea, dL.reshape(out.shape))
+        optimizer.step(self.gnn, self.last_grad_blob, lr)
+        return loss
+
+    def fit(self, dataset, **kw):
+        """The reference's ``trainer.fit`` without Lightning: see ``train.fit`` for the arguments."""
+        from .train import fit
+
+        return fit(self, dataset, **kw)
+
+    def save_checkpoint(self, path, epoch: int = 0, global_step: int = 0, optimizer=None, hparams: Optional[dict] = None):
+        """Write a checkpoint ``load_from_checkpoint`` reads weights-only: see ``train.save_checkpoint``."""
+        from .train import save_checkpoint
+
+        return save_checkpoint(self, path, epoch=epoch, global_step=global_step, optimizer=optimizer, hparams=hparams)
 
     def _assemble(self, sample: GraphSample, boo: torch.Tensor, block_output: Optional[bool]) -> DeviceMatrix:
         n = sample.num_nodes * self.block_size
