@@ -1,0 +1,746 @@
+// ==== batched lockstep ext_spai PCG (lspcg_batch_*) ===========================
+// A window of independent systems is laid out block-diagonally, every system's rows padded to
+// whole SpMV row tiles (256 block rows), and ONE launch per phase covers all of them: the split
+// schedule's five launches (KA, KB, UP, KC, UR) with
+//   * one row tile per workgroup (launch_spmv_sell_cfg one_tile_per_wg), so a workgroup's dot
+//     partial is its tile's and its prologue tests the tile's own system (done systems' tiles
+//     leave at once);
+//   * per-system last-arriver dot reductions (batch_sys_reduce): the last tile of a system to
+//     finish KB / KC sums the system's tile partials and updates its PcgState (scipy's scalars,
+//     the top-of-loop test, the iteration count), as the last-arriver schedule does for one system;
+//   * elementwise launches (UP, UR) of one 256-row tile per workgroup that read their system's
+//     finished scalars.
+// Padding rows are empty: they stay 0 in every vector and add exact zeros to the dots.
+//
+// The window is solved by an lspcg_solver of the block-diagonal system (lspcg_solver.hpp, created
+// in lspcg_pcg.hip); the loop's shared device code is in lspcg_pcg_kernels.hpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "lspcg_pcg_kernels.hpp"
+#include "lspcg_solver.hpp"
+
+using namespace lspcg;
+
+namespace lspcg {
+
+struct BatchMap {
+  const int32_t* etile_sys;  // [n / 256] system of each 256-row elementwise tile
+  const int32_t* tile0;      // [nsys + 1] first SpMV row tile (256 block rows) of each system
+  const int32_t* tk0;        // [nsys] first ticket line of each system: [top | group 0 | group 1 | ...]
+  int bs;                    // block size: SpMV tile b covers elementwise tiles bs*b .. bs*b + bs - 1
+};
+
+struct ProTile {
+  const PcgState* S;
+  BatchMap m;
+  __device__ __forceinline__ bool exit() const { return S[m.etile_sys[int64_t(blockIdx.x) * m.bs]].done != 0; }
+};
+
+// Per-system last-arriver reduction of a batched launch's N dots: each workgroup (= one row tile)
+// publishes its tile total (sc1 stores, drained, then relaxed agent-scope adds -- MI355X_MICROARCH.md
+// "Valid forms", table row 1, as grid_reduce_dd); the adds go to a two-level ticket (groups of
+// kTicketGroup tiles, then the system's top line: <= 32 serialised arrivals per line instead of a
+// system's few hundred -- the fan-in price), and the system's last arriving tile sums the system's
+// tile totals in tile order (fixed tree: the result does not depend on which tile came last);
+// thread 0 then runs fin(sys, values).  The elementwise launches read finished per-system scalars.
+template <int N, class Fin>
+__device__ __forceinline__ void batch_sys_reduce(DD (&v)[N], double* partials, unsigned* tickets, const BatchMap& m,
+                                                 Fin fin) {
+  __shared__ DD lds[16 * N];
+  __shared__ int s_last;
+  block_reduce_dd<N>(v, lds);
+  const int64_t tile = blockIdx.x;
+  const int sys = m.etile_sys[tile * m.bs];
+  const int t0 = m.tile0[sys], nt = m.tile0[sys + 1] - t0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      st_agent_f64(&partials[(size_t(tile) * N + j) * 2 + 0], v[j].s);
+      st_agent_f64(&partials[(size_t(tile) * N + j) * 2 + 1], v[j].c);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned* top = tickets + size_t(kTicketStride) * m.tk0[sys];
+    const unsigned g = unsigned(tile - t0) / kTicketGroup;
+    const unsigned gsize = min(unsigned(kTicketGroup), unsigned(nt) - g * kTicketGroup);
+    const unsigned ng = (unsigned(nt) + kTicketGroup - 1) / kTicketGroup;
+    unsigned* gt = top + size_t(kTicketStride) * (1 + g);
+    int last = 0;
+    if (__hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1) {
+      __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      last = __hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ng - 1;
+      if (last) __hip_atomic_store(top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    s_last = last;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  DD acc[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) acc[j] = dd_zero();
+  for (int b = threadIdx.x; b < nt; b += blockDim.x) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const size_t k = (size_t(t0 + b) * N + j) * 2;
+      acc[j] = dd_add(acc[j], DD{ld_agent_f64(&partials[k]), ld_agent_f64(&partials[k + 1])});
+    }
+  }
+  __syncthreads();
+  block_reduce_dd<N>(acc, lds);
+  if (threadIdx.x == 0) {
+    double out[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) out[j] = dd_value(acc[j]);
+    fin(sys, out);
+  }
+}
+
+// init: r_0 = b - A x0 ; ‖r_0‖², ‖b‖² -> the system's initial state (EpiResid::fin)
+template <typename T>
+struct EpiResidB {
+  static constexpr int NDOT = 2;
+  static constexpr bool CUSTOM_FINISH = true;
+  T* r;
+  const T* b;
+  PcgState* S;
+  double* partials;
+  unsigned* tickets;
+  BatchMap m;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
+    const T bi = gld(b + i);
+    const T ri = bi - s;
+    gst(r + i, ri);
+    dd_fma(dots[0], double(ri), double(ri));
+    dd_fma(dots[1], double(bi), double(bi));
+  }
+  __device__ __forceinline__ void finish(DD (&d)[2]) const {
+    PcgState* Sb = S;
+    batch_sys_reduce<2>(d, partials, tickets, m, [Sb](int sys, const double* v) {
+      PcgState* St = Sb + sys;
+      St->rr = round_to<T>(v[0]);
+      St->bb = round_to<T>(v[1]);
+      const double bn = double(tsqrt<T>(T(St->bb)));
+      St->atol = fmax(0.0, St->rtol * bn);
+      St->rho = St->rr;
+      St->alpha = 0.0;
+      St->iter = 0;
+      St->done = (bn == 0.0) ? 1 : 0;
+      if (St->hist) St->hist[0] = double(tsqrt<T>(T(St->rr)));
+    });
+  }
+};
+
+// KB: z = L t + ε r ; ρ_k = r·z, ‖r_k‖² -> the system's last arriver keeps ρ_k (EpiZ::fin) and runs
+// scipy's top-of-loop test on ‖r_k‖ (ProCheck / k_update_p_g): every tile of the system has
+// already passed this launch's prologue, so setting `done` here is seen first by UP
+template <typename T>
+struct EpiZB {
+  static constexpr int NDOT = 2;
+  static constexpr bool CUSTOM_FINISH = true;
+  T* z;
+  const T* r;
+  T eps;
+  PcgState* S;
+  double* partials;
+  unsigned* tickets;
+  BatchMap m;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
+    const T ri = gld(r + i);
+    const T zi = s + eps * ri;
+    gst(z + i, zi);
+    dd_fma(dots[0], double(ri), double(zi));
+    dd_fma(dots[1], double(ri), double(ri));
+  }
+  __device__ __forceinline__ void finish(DD (&d)[2]) const {
+    PcgState* Sb = S;
+    batch_sys_reduce<2>(d, partials, tickets, m, [Sb](int sys, const double* v) {
+      PcgState* St = Sb + sys;
+      St->rho_prev = St->rho;
+      St->rho = round_to<T>(v[0]);
+      const int64_t k = St->iter;
+      double rr = St->rr;  // ‖r_0‖² from the init
+      if (k > 0) {
+        rr = round_to<T>(v[1]);
+        St->rr = rr;
+        if (St->hist) St->hist[k] = double(tsqrt<T>(T(rr)));
+      }
+      int code = 0;
+      if (k >= St->max_iter) {
+        code = 2;
+      } else {
+        const double rn = double(tsqrt<T>(T(rr)));
+        if (rn < St->atol) code = 1;
+        else if (!(rn == rn) || rn == INFINITY) code = 3;
+      }
+      if (code) St->done = code;
+    });
+  }
+};
+
+// KC: q = A p ; π_k = p·q -> α_k = ρ_k/π_k, iteration k+1 (EpiQ<INC>::fin)
+template <typename T>
+struct EpiQB {
+  static constexpr int NDOT = 1;
+  static constexpr bool CUSTOM_FINISH = true;
+  T* q;
+  const T* p;
+  PcgState* S;
+  double* partials;
+  unsigned* tickets;
+  BatchMap m;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
+    gst(q + i, s);
+    dd_fma(dots[0], double(gld(p + i)), double(s));
+  }
+  __device__ __forceinline__ void finish(DD (&d)[1]) const {
+    PcgState* Sb = S;
+    batch_sys_reduce<1>(d, partials, tickets, m, [Sb](int sys, const double* v) {
+      PcgState* St = Sb + sys;
+      const double pq = round_to<T>(v[0]);
+      St->pq = pq;
+      St->alpha = double(T(St->rho) / T(pq));
+      St->iter = St->iter + 1;
+    });
+  }
+};
+
+// UP: x += α_{k-1} p_{k-1} (k > 0) ; p_k = p_{k-1}β + z with β = ρ_k/ρ_{k-1} (k_update_p_g's
+// expressions), one 256-row tile of one system per workgroup
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_batch_update_p(BatchMap m, const PcgState* S, const T* __restrict__ z,
+                                                             T* __restrict__ p, T* __restrict__ x) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  const T zi = z[i], pi = p[i], xi = x[i];
+  const PcgState* St = S + m.etile_sys[blockIdx.x];
+  if (St->done) return;
+  const bool first = St->iter == 0;
+  const T beta = first ? T(0) : T(St->rho) / T(St->rho_prev);
+  const T alpha = T(St->alpha);
+  if (!first) x[i] = xi + alpha * pi;
+  p[i] = first ? zi : (pi * beta) + zi;
+}
+
+// UR: r_{k+1} = r_k - α_k q
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_batch_update_r(BatchMap m, const PcgState* S, const T* __restrict__ q,
+                                                             T* __restrict__ r) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  const T ri = r[i], qi = q[i];
+  const PcgState* St = S + m.etile_sys[blockIdx.x];
+  if (St->done) return;
+  r[i] = ri - T(St->alpha) * qi;
+}
+
+// ---- consumer-sum mode (windows whose systems have <= 128 tiles each): KB / KC only store
+// per-tile partials (grid_partial_groups, gsz = 1: no tickets) and every UP / UR workgroup sums its
+// system's tile partials itself (group_sum_dd, one wave for <= 256) ------------------------------
+// init: r_0 = b - A x0 ; per-tile partials of ‖r_0‖², ‖b‖²
+template <typename T>
+struct EpiResidTile {
+  static constexpr int NDOT = 2;
+  static constexpr bool GROUPS = true;
+  T* r;
+  const T* b;
+  double* partials;
+  unsigned* ticket;
+  double* group_out;
+  int gsz;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
+    const T bi = gld(b + i);
+    const T ri = bi - s;
+    gst(r + i, ri);
+    dd_fma(dots[0], double(ri), double(ri));
+    dd_fma(dots[1], double(bi), double(bi));
+  }
+  __device__ __forceinline__ void fin(const double*) const {}
+};
+
+// one workgroup per system: the init state from the system's tile partials (EpiResid::fin)
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_batch_init(PcgState* S, const int32_t* __restrict__ tile0,
+                                                         const double* __restrict__ gi) {
+  const int sys = blockIdx.x;
+  const int t0 = tile0[sys], t1 = tile0[sys + 1];
+  double v[2];
+  group_sum_dd<2>(gi + size_t(t0) * 4, t1 - t0, v);
+  if (threadIdx.x) return;
+  PcgState* St = S + sys;
+  St->rr = round_to<T>(v[0]);
+  St->bb = round_to<T>(v[1]);
+  const double bn = double(tsqrt<T>(T(St->bb)));
+  St->atol = fmax(0.0, St->rtol * bn);
+  St->rho = St->rr;
+  St->alpha = 0.0;
+  St->iter = 0;
+  St->done = (bn == 0.0) ? 1 : 0;
+  if (St->hist) St->hist[0] = double(tsqrt<T>(T(St->rr)));
+}
+
+// consumer-sum mode: UP of the split schedule (k_update_p_g) for the tile's system, summing the
+// system's tile partials itself
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_batch_update_p_sums(BatchMap m, PcgState* S, const double* __restrict__ gz,
+                                                             const T* __restrict__ z, T* __restrict__ p,
+                                                             T* __restrict__ x) {
+  const int sys = m.etile_sys[blockIdx.x];
+  PcgState* St = S + sys;
+  // `done` is loaded once and tested only after the group sums: group_sum_dd may hold workgroup
+  // barriers, and this system's first workgroup can write `done` during this launch
+  const int32_t done = St->done;
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  const T zi = z[i], pi = p[i], xi = x[i];
+  const int t0 = m.tile0[sys], t1 = m.tile0[sys + 1];
+  const int64_t k = St->iter;
+  double v[2];
+  group_sum_dd<2>(gz + size_t(t0) * 4, t1 - t0, v);
+  if (done) return;
+  const double rho = round_to<T>(v[0]);
+  const double rr = k > 0 ? round_to<T>(v[1]) : St->rr;
+  int code = 0;
+  if (k >= St->max_iter) {
+    code = 2;
+  } else {
+    const double rn = double(tsqrt<T>(T(rr)));
+    if (rn < St->atol) code = 1;
+    else if (!(rn == rn) || rn == INFINITY) code = 3;
+  }
+  if (int64_t(blockIdx.x) == int64_t(t0) * m.bs && threadIdx.x == 0) {
+    if (k > 0) {
+      St->rr = rr;
+      if (St->hist) St->hist[k] = double(tsqrt<T>(T(rr)));
+    }
+    if (code) St->done = code;
+  }
+  if (code) return;
+  const bool first = k == 0;
+  const T beta = first ? T(0) : T(rho) / T(St->rho);
+  const T alpha = T(St->alpha);
+  if (!first) x[i] = xi + alpha * pi;
+  p[i] = first ? zi : (pi * beta) + zi;
+}
+
+// consumer-sum mode: UR of the split schedule (k_update_r_g) for the tile's system
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_batch_update_r_sums(BatchMap m, PcgState* S, const double* __restrict__ gz,
+                                                             const double* __restrict__ gq, const T* __restrict__ q,
+                                                             T* __restrict__ r) {
+  const int sys = m.etile_sys[blockIdx.x];
+  PcgState* St = S + sys;
+  if (St->done) return;
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  const T ri = r[i], qi = q[i];
+  const int t0 = m.tile0[sys], t1 = m.tile0[sys + 1];
+  double vz[2], vq[1];
+  group_sum_dd<2>(gz + size_t(t0) * 4, t1 - t0, vz);
+  group_sum_dd<1>(gq + size_t(t0) * 2, t1 - t0, vq);
+  const double rho = round_to<T>(vz[0]);
+  const double pq = round_to<T>(vq[0]);
+  const T alpha = T(rho) / T(pq);
+  if (int64_t(blockIdx.x) == int64_t(t0) * m.bs && threadIdx.x == 0) {
+    St->rho_prev = St->rho;
+    St->rho = rho;
+    St->pq = pq;
+    St->alpha = double(alpha);
+    St->iter = St->iter + 1;
+  }
+  r[i] = ri - alpha * qi;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_batch_x_fixup(BatchMap m, const PcgState* S, const T* __restrict__ p,
+                                                            T* __restrict__ x) {
+  const PcgState* St = S + m.etile_sys[blockIdx.x];
+  if (St->iter < 1 || St->bb == 0.0) return;
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  x[i] = x[i] + T(St->alpha) * p[i];
+}
+
+// block-diagonal assembly: rows [0, cnt) of one system at its row offset (rows >= nb empty)
+__global__ void k_cat_rowptr(int64_t cnt, int64_t nb, const int32_t* __restrict__ rp, int32_t e0,
+                             int32_t* __restrict__ out) {
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < cnt; i += int64_t(gridDim.x) * blockDim.x)
+    out[i] = rp[i < nb ? i : nb] + e0;
+}
+__global__ void k_cat_colind(int64_t nnz, const int32_t* __restrict__ c, int32_t off, int32_t* __restrict__ out) {
+  for (int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < nnz; k += int64_t(gridDim.x) * blockDim.x)
+    out[k] = c[k] + off;
+}
+
+}  // namespace lspcg
+
+struct lspcg_batch {
+  lspcg_ctx* ctx = nullptr;
+  int nsys = 0;
+  int bs = 1;
+  int dtype = LSPCG_F64;
+  lspcg_mat* Acat = nullptr;
+  lspcg_mat* Lcat = nullptr;
+  lspcg_solver* s = nullptr;  // solver of the block-diagonal system: views, vectors, stream
+  std::vector<int64_t> off, n;  // scalar row offset and size of every system
+  int64_t ntot = 0;             // padded scalar rows
+  int32_t* etile_sys = nullptr;
+  int32_t* tile0 = nullptr;
+  int32_t* tk0 = nullptr;
+  double* partials = nullptr;  // per-tile dot partials (<= 2 dots, DD each)
+  unsigned* tickets = nullptr;  // per system: top line + one line per kTicketGroup tiles (batch_sys_reduce)
+  bool sums = false;            // consumer-sum reductions (every system <= 128 tiles; LSPCG_BATCH_REDUCE)
+  bool small = false;           // every system fits the one-workgroup solve: one launch, one workgroup per system
+  int64_t max_n = 0;
+  int32_t* boff = nullptr;      // [nsys] scalar row offset / size of each system (small mode)
+  int32_t* bn = nullptr;
+  double* gsum = nullptr;       // consumer-sum partials: init (2 dots) | KB (2 dots) | KC (1 dot), per tile
+  int64_t ntiles = 0;
+  PcgState* S = nullptr;
+  PcgState* hS = nullptr;  // pinned: 2 poll slots x nsys
+  double* dhist = nullptr;
+  int64_t dhist_cap = 0;
+  lspcg::IterationGraphs graphs;  // of enqueue_batch_iteration
+};
+
+namespace lspcg {
+
+static BatchMap batch_map(const lspcg_batch* bt) { return BatchMap{bt->etile_sys, bt->tile0, bt->tk0, bt->bs}; }
+
+// SpMV of iteration view w over the block-diagonal system, one row tile per workgroup
+template <typename T, class Pro, class Epi>
+static int launch_it_tiles(lspcg_solver* s, int w, const T* x, Pro pro, Epi epi, hipStream_t st) {
+  const SellPattern* P = s->sp[w];
+  if (!P) return LSPCG_ERR_UNSUPPORTED;
+  if constexpr (sizeof(T) == 8) {
+    if (s->svd[w] == LSPCG_F32) {
+      launch_spmv_sell_cfg<T, float>(*P, s->sv[w], GatherVec<T>{x}, pro, epi, st, true);
+      return LSPCG_OK;
+    }
+  }
+  launch_spmv_sell_cfg<T, T>(*P, s->sv[w], GatherVec<T>{x}, pro, epi, st, true);
+  return LSPCG_OK;
+}
+
+template <typename T>
+static int enqueue_batch_init(lspcg_batch* bt, hipStream_t st) {
+  lspcg_solver* s = bt->s;
+  if (bt->sums) {
+    int rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(s->x), ProNone{},
+                                EpiResidTile<T>{static_cast<T*>(s->r), static_cast<const T*>(s->b), nullptr, nullptr,
+                                                bt->gsum, 1},
+                                st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_batch_init<T>, dim3(bt->nsys), dim3(kThreads), 0, st, bt->S,
+                       static_cast<const int32_t*>(bt->tile0), static_cast<const double*>(bt->gsum));
+    LSPCG_HIP(hipGetLastError());
+    return LSPCG_OK;
+  }
+  return launch_it_tiles<T>(s, 0, static_cast<const T*>(s->x), ProNone{},
+                            EpiResidB<T>{static_cast<T*>(s->r), static_cast<const T*>(s->b), bt->S, bt->partials,
+                                         bt->tickets, batch_map(bt)},
+                            st);
+}
+
+template <typename T>
+static int enqueue_batch_iteration(lspcg_batch* bt, hipStream_t st) {
+  lspcg_solver* s = bt->s;
+  T* x = static_cast<T*>(s->x);
+  T* r = static_cast<T*>(s->r);
+  T* z = static_cast<T*>(s->z);
+  T* t = static_cast<T*>(s->t);
+  T* p = static_cast<T*>(s->p);
+  T* q = static_cast<T*>(s->q);
+  const BatchMap m = batch_map(bt);
+  const ProTile pro{bt->S, m};
+  const dim3 eg(unsigned(bt->ntot / kThreads));
+  int rc = launch_it_tiles<T>(s, 2, static_cast<const T*>(r), pro, EpiT<T, false>{t, nullptr}, st);
+  if (rc) return rc;
+  if (bt->sums) {
+    double* gz = bt->gsum + 4 * bt->ntiles;
+    double* gq = bt->gsum + 8 * bt->ntiles;
+    rc = launch_it_tiles<T>(s, 1, static_cast<const T*>(t), pro,
+                            EpiZG<T, false>{z, r, nullptr, T(s->eps), nullptr, nullptr, gz, 1}, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_batch_update_p_sums<T>, eg, dim3(kThreads), 0, st, m, bt->S, static_cast<const double*>(gz),
+                       static_cast<const T*>(z), p, x);
+    rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(p), pro, EpiQG<T>{q, p, nullptr, nullptr, gq, 1}, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_batch_update_r_sums<T>, eg, dim3(kThreads), 0, st, m, bt->S, static_cast<const double*>(gz),
+                       static_cast<const double*>(gq), static_cast<const T*>(q), r);
+    LSPCG_HIP(hipGetLastError());
+    return LSPCG_OK;
+  }
+  rc = launch_it_tiles<T>(s, 1, static_cast<const T*>(t), pro,
+                          EpiZB<T>{z, r, T(s->eps), bt->S, bt->partials, bt->tickets, m}, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_batch_update_p<T>, eg, dim3(kThreads), 0, st, m, static_cast<const PcgState*>(bt->S),
+                     static_cast<const T*>(z), p, x);
+  rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(p), pro, EpiQB<T>{q, p, bt->S, bt->partials, bt->tickets, m},
+                          st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_batch_update_r<T>, eg, dim3(kThreads), 0, st, m, static_cast<const PcgState*>(bt->S),
+                     static_cast<const T*>(q), r);
+  LSPCG_HIP(hipGetLastError());
+  return LSPCG_OK;
+}
+
+// every system of the window in its own workgroup (k_pcg_small in batch mode): the whole loop in
+// one launch; rows per thread / threads from the window's largest system (launch_small's rule)
+template <typename T>
+static int launch_batch_small(lspcg_batch* bt, hipStream_t st) {
+  lspcg_solver* s = bt->s;
+  const CsrView A = csr_view(s, 0, s->Av), L = csr_view(s, 1, s->Lv), LT = csr_view(s, 2, s->LTv);
+  auto* x = static_cast<T*>(s->x);
+  auto* r = static_cast<T*>(s->r);
+  auto* p = static_cast<T*>(s->p);
+  const T* d = static_cast<const T*>(s->d);
+  const int64_t n = bt->max_n;
+  const dim3 g(unsigned(bt->nsys));
+  const size_t lds = 3 * sizeof(T) * size_t(n);
+  auto go = [&](auto rows, auto threads) {
+    constexpr int R = decltype(rows)::value;
+    constexpr int TH = decltype(threads)::value;
+    hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_EXT_SPAI, R, TH>), g, dim3(TH), lds, st, int32_t(n), bt->S, A, L,
+                       LT, d, x, r, p, static_cast<const int32_t*>(bt->boff), static_cast<const int32_t*>(bt->bn));
+  };
+  dispatch_small(n, go);
+  LSPCG_HIP(hipGetLastError());
+  return LSPCG_OK;
+}
+
+// block-diagonal copy of M[0..nsys) with system k's block rows starting at brow[k] (padded)
+static int cat_matrices(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* M, const std::vector<int64_t>& brow,
+                        lspcg_mat** out) {
+  const int bs = M[0]->block_size;
+  int64_t nnz = 0;
+  for (int k = 0; k < nsys; ++k) nnz += M[k]->nnzb;
+  LSPCG_CHECK(nnz < (int64_t(1) << 31), LSPCG_ERR_ARG, "batch: more than 2^31 stored blocks in the window");
+  lspcg_mat* C = nullptr;
+  if (int rc = mat_alloc(ctx, brow[nsys], nnz, bs, M[0]->dtype, &C)) return rc;
+  hipStream_t st = ctx->stream;
+  const size_t vb = (M[0]->dtype == LSPCG_F32 ? 4 : 8) * size_t(bs) * bs;
+  int64_t e0 = 0;
+  for (int k = 0; k < nsys; ++k) {
+    const int64_t cnt = brow[k + 1] - brow[k] + (k == nsys - 1 ? 1 : 0);
+    hipLaunchKernelGGL(k_cat_rowptr, dim3(unsigned(std::min<int64_t>((cnt + 255) / 256, 1024))), dim3(256), 0, st, cnt,
+                       M[k]->nb, static_cast<const int32_t*>(M[k]->rowptr), int32_t(e0), C->rowptr + brow[k]);
+    if (M[k]->nnzb) {
+      hipLaunchKernelGGL(k_cat_colind, dim3(unsigned(std::min<int64_t>((M[k]->nnzb + 255) / 256, 1024))), dim3(256), 0,
+                         st, M[k]->nnzb, static_cast<const int32_t*>(M[k]->colind), int32_t(brow[k]), C->colind + e0);
+      LSPCG_HIP(hipMemcpyAsync(static_cast<char*>(C->vals) + vb * e0, M[k]->vals, vb * M[k]->nnzb,
+                               hipMemcpyDeviceToDevice, st));
+    }
+    e0 += M[k]->nnzb;
+  }
+  LSPCG_HIP(hipGetLastError());
+  LSPCG_HIP(hipStreamSynchronize(st));
+  *out = C;
+  return LSPCG_OK;
+}
+
+}  // namespace lspcg
+
+extern "C" {
+
+int lspcg_batch_destroy(lspcg_batch* bt) {
+  if (!bt) return LSPCG_OK;
+  (void)hipSetDevice(bt->ctx->device);
+  if (bt->s) (void)hipStreamSynchronize(bt->s->stream);
+  bt->graphs.clear();
+  if (bt->s) lspcg_solver_destroy(bt->s);
+  if (bt->Acat) lspcg_mat_destroy(bt->Acat);
+  if (bt->Lcat) lspcg_mat_destroy(bt->Lcat);
+  for (void* v : {(void*)bt->boff, (void*)bt->bn, (void*)bt->etile_sys, (void*)bt->tile0, (void*)bt->tk0, (void*)bt->gsum, (void*)bt->partials, (void*)bt->tickets, (void*)bt->S,
+                  (void*)bt->dhist})
+    (void)hipFree(v);
+  (void)hipHostFree(bt->hS);
+  delete bt;
+  return LSPCG_OK;
+}
+
+int lspcg_batch_create(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, const lspcg_mat* const* L,
+                       double epsilon, lspcg_batch** out) {
+  LSPCG_CHECK(ctx && A && L && out && nsys >= 1, LSPCG_ERR_ARG, "batch_create: NULL argument or nsys < 1");
+  for (int k = 0; k < nsys; ++k) {
+    LSPCG_CHECK(A[k] && L[k], LSPCG_ERR_ARG, "batch_create: NULL matrix " + std::to_string(k));
+    LSPCG_CHECK(A[k]->dtype == A[0]->dtype && L[k]->dtype == A[0]->dtype, LSPCG_ERR_ARG,
+                "batch_create: every A and L must have one dtype");
+    LSPCG_CHECK(A[k]->block_size == A[0]->block_size && L[k]->block_size == A[0]->block_size, LSPCG_ERR_ARG,
+                "batch_create: every A and L must have one block size");
+    LSPCG_CHECK(L[k]->n == A[k]->n && A[k]->n >= 1, LSPCG_ERR_ARG,
+                "batch_create: system " + std::to_string(k) + ": L and A differ in size or are empty");
+  }
+  LSPCG_HIP(hipSetDevice(ctx->device));
+  std::unique_ptr<lspcg_batch, int (*)(lspcg_batch*)> bt(new lspcg_batch(), lspcg_batch_destroy);
+  bt->ctx = ctx;
+  bt->nsys = nsys;
+  bt->bs = A[0]->block_size;
+  bt->dtype = A[0]->dtype;
+  // block-row offsets, each system padded to whole SpMV row tiles (kSellWG block rows)
+  std::vector<int64_t> brow(nsys + 1, 0);
+  for (int k = 0; k < nsys; ++k) brow[k + 1] = brow[k] + (A[k]->nb + kSellWG - 1) / kSellWG * kSellWG;
+  LSPCG_CHECK(brow[nsys] * bt->bs < (int64_t(1) << 31), LSPCG_ERR_ARG, "batch_create: window exceeds 2^31 rows");
+  for (int k = 0; k < nsys; ++k) {
+    bt->off.push_back(brow[k] * bt->bs);
+    bt->n.push_back(A[k]->n);
+  }
+  bt->ntot = brow[nsys] * bt->bs;
+  if (int rc = cat_matrices(ctx, nsys, A, brow, &bt->Acat)) return rc;
+  if (int rc = cat_matrices(ctx, nsys, L, brow, &bt->Lcat)) return rc;
+  // one workgroup per system when every system fits the one-workgroup solve (scalar views; its
+  // row and LDS bounds, small_path); LSPCG_BATCH_SMALL=0 keeps the lockstep phases.  Decided before
+  // the views are built: that mode reads 4-entry-group SELL copies, not SELL-DIA
+  for (int k = 0; k < nsys; ++k) bt->max_n = std::max<int64_t>(bt->max_n, bt->n[k]);
+  {
+    const char* e = std::getenv("LSPCG_BATCH_SMALL");
+    const char* en = std::getenv("LSPCG_SMALL_N");
+    const int64_t small_n = en ? std::max<int64_t>(0, std::atoll(en)) : kSmallNDefault;
+    const int64_t row_cap = int64_t(kSmallThreadsBig) * 3;
+    bt->small = !(e && e[0] == '0') && bt->bs == 1 && bt->max_n <= std::min<int64_t>(row_cap, small_n) &&
+                3 * bt->max_n * int64_t(esize(bt->dtype)) <= kSmallLds;
+  }
+  if (int rc = solver_create(ctx, bt->Acat, LSPCG_PRECOND_EXT_SPAI, !bt->small, false, &bt->s)) return rc;
+  if (int rc = lspcg_solver_set_spai(bt->s, bt->Lcat, epsilon, nullptr)) return rc;
+  LSPCG_CHECK(bt->s->sp[0] && bt->s->sp[1] && bt->s->sp[2], LSPCG_ERR_UNSUPPORTED,
+              "batch_create: no SELL view of the block-diagonal system (irregular rows): solve one by one");
+  // tile maps
+  const int64_t ntiles = brow[nsys] / kSellWG;
+  std::vector<int32_t> esys(size_t(bt->ntot / kThreads)), t0(nsys + 1);
+  for (int k = 0; k < nsys; ++k) {
+    t0[k] = int32_t(brow[k] / kSellWG);
+    for (int64_t e = bt->off[k] / kThreads; e < (bt->off[k] + (brow[k + 1] - brow[k]) * bt->bs) / kThreads; ++e)
+      esys[size_t(e)] = k;
+  }
+  t0[nsys] = int32_t(ntiles);
+  std::vector<int32_t> tk(nsys);
+  int64_t lines = 0;
+  for (int k = 0; k < nsys; ++k) {
+    tk[k] = int32_t(lines);
+    lines += 1 + (t0[k + 1] - t0[k] + kTicketGroup - 1) / kTicketGroup;
+  }
+  LSPCG_HIP(hipMalloc(&bt->tk0, sizeof(int32_t) * nsys));
+  LSPCG_HIP(hipMemcpy(bt->tk0, tk.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
+  LSPCG_HIP(hipMalloc(&bt->etile_sys, sizeof(int32_t) * esys.size()));
+  LSPCG_HIP(hipMalloc(&bt->tile0, sizeof(int32_t) * t0.size()));
+  LSPCG_HIP(hipMemcpy(bt->etile_sys, esys.data(), sizeof(int32_t) * esys.size(), hipMemcpyHostToDevice));
+  LSPCG_HIP(hipMemcpy(bt->tile0, t0.data(), sizeof(int32_t) * t0.size(), hipMemcpyHostToDevice));
+  LSPCG_HIP(hipMalloc(&bt->partials, sizeof(double) * 4 * ntiles));
+  // reductions: consumer sums when every system has <= 128 tiles (C5 heat, <= 117 tiles: 25.6 vs
+  // 26.8 us per lockstep iteration), else per-system last arrivers (8 x Poisson 256^2, 256 tiles:
+  // 47.1 vs 49.9); LSPCG_BATCH_REDUCE=0 / 1 forces either
+  int max_nt = 0;
+  for (int k = 0; k < nsys; ++k) max_nt = std::max(max_nt, t0[k + 1] - t0[k]);
+  bt->sums = max_nt <= 128;
+  if (const char* e = std::getenv("LSPCG_BATCH_REDUCE")) bt->sums = e[0] == '1';
+  bt->ntiles = ntiles;
+  LSPCG_HIP(hipMalloc(&bt->gsum, sizeof(double) * 10 * ntiles));
+  if (bt->small) {
+    std::vector<int32_t> ho(nsys), hn(nsys);
+    for (int k = 0; k < nsys; ++k) {
+      ho[k] = int32_t(bt->off[k]);
+      hn[k] = int32_t(bt->n[k]);
+    }
+    LSPCG_HIP(hipMalloc(&bt->boff, sizeof(int32_t) * nsys));
+    LSPCG_HIP(hipMalloc(&bt->bn, sizeof(int32_t) * nsys));
+    LSPCG_HIP(hipMemcpy(bt->boff, ho.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
+    LSPCG_HIP(hipMemcpy(bt->bn, hn.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
+  }
+  LSPCG_HIP(hipMalloc(&bt->tickets, sizeof(unsigned) * kTicketStride * lines));
+  LSPCG_HIP(hipMemset(bt->tickets, 0, sizeof(unsigned) * kTicketStride * lines));
+  LSPCG_HIP(hipMalloc(&bt->S, sizeof(PcgState) * nsys));
+  LSPCG_HIP(hipHostMalloc(&bt->hS, 2 * sizeof(PcgState) * nsys, hipHostMallocDefault));
+  *out = bt.release();
+  return LSPCG_OK;
+}
+
+int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, double rtol, int64_t max_iter,
+                      int64_t* iters, int32_t* status, double* const* res_hist, double* t_solve_ms) {
+  LSPCG_CHECK(bt && b && x && iters && status, LSPCG_ERR_ARG, "batch_solve: NULL argument");
+  const int ns = bt->nsys;
+  for (int k = 0; k < ns; ++k) LSPCG_CHECK(b[k] && x[k], LSPCG_ERR_ARG, "batch_solve: NULL vector " + std::to_string(k));
+  lspcg_solver* s = bt->s;
+  LSPCG_HIP(hipSetDevice(bt->ctx->device));
+  hipStream_t st = s->stream;
+  const size_t es = esize(bt->dtype);
+  std::vector<int64_t> mi(ns), hoff(ns + 1, 0);
+  for (int k = 0; k < ns; ++k) {
+    mi[k] = max_iter > 0 ? max_iter : bt->n[k];
+    hoff[k + 1] = hoff[k] + ((res_hist && res_hist[k]) ? mi[k] + 2 : 0);
+  }
+  if (hoff[ns] > bt->dhist_cap) {
+    LSPCG_HIP(hipStreamSynchronize(st));
+    (void)hipFree(bt->dhist);
+    bt->dhist = nullptr;
+    bt->dhist_cap = 0;
+    LSPCG_HIP(hipMalloc(&bt->dhist, sizeof(double) * hoff[ns]));
+    bt->dhist_cap = hoff[ns];
+  }
+  std::unique_lock<std::mutex> sub(submit_mutex());  // as in lspcg_solver_solve
+  LSPCG_HIP(hipEventRecord(s->ev_in, bt->ctx->stream));
+  LSPCG_HIP(hipStreamWaitEvent(st, s->ev_in, 0));
+  LSPCG_HIP(hipEventRecord(s->ev_t0, st));
+  char* cb = static_cast<char*>(s->b);
+  char* cx = static_cast<char*>(s->x);
+  for (int k = 0; k < ns; ++k) {  // padding rows stay 0 (zeroed at creation, never written)
+    LSPCG_HIP(hipMemcpyAsync(cb + es * bt->off[k], b[k], es * bt->n[k], hipMemcpyDeviceToDevice, st));
+    LSPCG_HIP(hipMemcpyAsync(cx + es * bt->off[k], x[k], es * bt->n[k], hipMemcpyDeviceToDevice, st));
+  }
+  for (int k = 0; k < ns; ++k)
+    bt->hS[k] = initial_state(rtol, s->eps, (res_hist && res_hist[k]) ? bt->dhist + hoff[k] : nullptr, mi[k]);
+  LSPCG_HIP(hipMemcpyAsync(bt->S, bt->hS, sizeof(PcgState) * ns, hipMemcpyHostToDevice, st));
+  int rc = bt->dtype == LSPCG_F64 ? enqueue_batch_init<double>(bt, st) : enqueue_batch_init<float>(bt, st);
+  if (rc) return rc;
+
+  // every system's state through the poll loop (small mode: one launch)
+  StatePoll poll{ns, bt->S, bt->hS, {s->ev_poll, s->ev_poll2}, st, sub};
+  std::vector<PcgState> cur(ns);
+  if (bt->small) {
+    rc = bt->dtype == LSPCG_F64 ? launch_batch_small<double>(bt, st) : launch_batch_small<float>(bt, st);
+    if (!rc) rc = poll.post();
+    if (!rc) rc = poll.take(cur.data());
+  } else {
+    auto one = [&] {
+      return bt->dtype == LSPCG_F64 ? enqueue_batch_iteration<double>(bt, st) : enqueue_batch_iteration<float>(bt, st);
+    };
+    rc = poll.run(mi.data(), 32, [&](int c) { return bt->graphs.launch(st, c, one); }, cur.data());
+  }
+  if (rc) return rc;
+  const BatchMap m = batch_map(bt);
+  if (bt->dtype == LSPCG_F64)
+    hipLaunchKernelGGL(k_batch_x_fixup<double>, dim3(unsigned(bt->ntot / kThreads)), dim3(kThreads), 0, st, m, bt->S,
+                       static_cast<const double*>(s->p), static_cast<double*>(s->x));
+  else
+    hipLaunchKernelGGL(k_batch_x_fixup<float>, dim3(unsigned(bt->ntot / kThreads)), dim3(kThreads), 0, st, m, bt->S,
+                       static_cast<const float*>(s->p), static_cast<float*>(s->x));
+  LSPCG_HIP(hipGetLastError());
+  for (int k = 0; k < ns; ++k) {
+    const char* src = (cur[k].bb == 0.0) ? cb : cx;  // scipy returns b when ‖b‖ = 0
+    LSPCG_HIP(hipMemcpyAsync(x[k], src + es * bt->off[k], es * bt->n[k], hipMemcpyDeviceToDevice, st));
+  }
+  LSPCG_HIP(hipEventRecord(s->ev_t1, st));
+  LSPCG_HIP(hipEventRecord(s->ev_out, st));
+  LSPCG_HIP(hipStreamWaitEvent(bt->ctx->stream, s->ev_out, 0));
+  LSPCG_HIP(poll.wait(s->ev_t1));
+  float ms = 0.f;
+  LSPCG_HIP(hipEventElapsedTime(&ms, s->ev_t0, s->ev_t1));
+  if (t_solve_ms) *t_solve_ms = ms;
+  bool all = true;
+  for (int k = 0; k < ns; ++k) {
+    const PcgState& f = cur[k];
+    const SolveTail tail(f, mi[k]);
+    iters[k] = tail.iters;
+    status[k] = f.done == 1 ? LSPCG_OK : LSPCG_NOT_CONVERGED;
+    all = all && f.done == 1;
+    if (res_hist && res_hist[k]) {
+      LSPCG_HIP(hipMemcpy(res_hist[k], bt->dhist + hoff[k], sizeof(double) * tail.written, hipMemcpyDeviceToHost));
+      tail.nan_fill(res_hist[k]);
+    }
+  }
+  return all ? LSPCG_OK : LSPCG_NOT_CONVERGED;
+}
+
+}  // extern "C"

@@ -122,6 +122,13 @@ struct SellPattern {
   int kx = 0;                      // SELL-64X: the longest list
   int64_t xn = 0;                  // SELL-64X: vector entries read (largest column + 1; > n for dist_pcg's halo)
   const int32_t* rowptr = nullptr; // CSR row pointer (row lengths), not owned
+  // Every field above, pointers and values alike, to f: what a launch captured in a graph holds of
+  // the pattern (the solver's graph_key).  A new field belongs in the list above AND here.
+  template <class F>
+  void each_field(F f) const {
+    f(n), f(nb), f(bs), f(ns), f(groups), f(gp), f(col), f(col_bits), f(dict), f(rgp), f(col2), f(lmap), f(jc);
+    f(elems), f(xlp), f(xl), f(kx), f(xn), f(rowptr);
+  }
   // the jagged element layout (SELL-64J / SELL-64X): gp is an element prefix
   bool jagged() const { return col_bits == kSellJag || col_bits == kSellJagX; }
   // entries of a value array of this pattern (sell_fill_values allocates this many)
@@ -129,25 +136,12 @@ struct SellPattern {
     if (bs == 3) return int64_t(576) * groups;  // BSELL-64 / BSELL-DIA: 9 values per block slot
     return jagged() ? elems : (col_bits == 1 ? int64_t(64) : int64_t(256)) * groups;
   }
-  void release() {
-    (void)hipFree(gp);
-    (void)hipFree(col);
-    (void)hipFree(dict);
-    (void)hipFree(rgp);
-    (void)hipFree(col2);
-    (void)hipFree(lmap);
-    (void)hipFree(jc);
-    (void)hipFree(xlp);
-    (void)hipFree(xl);
-    xlp = nullptr;
-    xl = nullptr;
-    gp = nullptr;
-    col = nullptr;
-    dict = nullptr;
-    rgp = nullptr;
-    col2 = nullptr;
-    lmap = nullptr;
-    jc = nullptr;
+  void release() {  // the owned arrays (not rowptr)
+    auto drop = [](auto*& p) {
+      (void)hipFree(p);
+      p = nullptr;
+    };
+    drop(gp), drop(col), drop(dict), drop(rgp), drop(col2), drop(lmap), drop(jc), drop(xlp), drop(xl);
   }
 };
 

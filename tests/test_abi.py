@@ -34,6 +34,17 @@ def test_library_exports_every_declared_symbol():
     assert lib.lspcg_version() >= 10000
 
 
+def test_build_lists_every_source_and_header():
+    """csrc/ holds exactly the units and headers _build names, so tree_hash() covers every file the
+    library is compiled from: a header missing from HEADERS would let a stale library be reused."""
+    from learningsparsepreconditioner4gpu_amd import _build
+
+    present = {p.name for p in _build.CSRC.iterdir() if p.suffix in (".hip", ".hpp")}
+    listed = _build.SOURCES + _build.HEADERS
+    assert len(set(listed)) == len(listed)
+    assert present == set(listed), present ^ set(listed)
+
+
 def test_no_gpu_fails_loudly():
     import torch
 

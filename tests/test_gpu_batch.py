@@ -81,6 +81,39 @@ def test_batch_matches_single_and_oracle(gpu_ctx, monkeypatch, reduce):
     print(f"batch iterates bit-identical to single solves: {same_bits}/{len(As)}")
 
 
+@pytest.fixture(scope="module")
+def poisson64():
+    """Poisson 64 x 64 (n = 4,096: above the one-workgroup solve's 2,560 rows, so graph-captured
+    chunks and the chunk predictor run) and the oracle's exact-dot history of the unbounded solve."""
+    A = P.poisson2d_grid(64, 64)[0]
+    L = _cases.spai_like(A, seed=3)
+    b = A @ np.ones(A.shape[0])
+    it_o, _, h_o = O.pcg(sp.csr_matrix(A), b, O.spai_operator(sp.csr_matrix(L), 3e-3), rtol=1e-8, dot="exact")
+    return A, L, b, it_o, np.asarray(h_o)
+
+
+@pytest.mark.parametrize("max_iter", [1, 5, 37, 0])
+def test_poll_loop_one_system_equals_batch_of_one(gpu_ctx, poisson64, max_iter):
+    """The single solve and a batch of one system run the same poll loop: the same count, status and
+    history, which is the oracle's.  max_iter 5 and 37 stop inside a chunk (chunks are powers of
+    two); 0 is the unbounded solve."""
+    A, L, b, it_o, h_o = poisson64
+    assert A.shape[0] > 2560
+    it1, conv1, _, h1 = _single(A, L, b, 3e-3, 1e-8, max_iter=max_iter)
+    _, res, _ = _batch([A], [L], [b], 3e-3, 1e-8, max_iter=max_iter)
+    it, conv, h = res[0]
+    print(f"max_iter {max_iter}: single {it1} {conv1}, batch {it} {conv}, oracle {it_o}; history bits equal: "
+          f"{np.array_equal(h, h1)}, max rel diff to the oracle {np.max(np.abs(h1 - h_o[:len(h1)]) / h_o[:len(h1)]):.3e}")
+    assert (it, conv) == (it1, conv1)
+    assert np.array_equal(h, h1)
+    if max_iter:
+        assert it1 == max_iter < it_o and not conv1
+    else:
+        assert it1 == it_o and conv1
+    assert len(h1) == it1 + 1
+    np.testing.assert_allclose(h1, h_o[:it1 + 1], rtol=1e-12, atol=0)
+
+
 def test_batch_fp32(gpu_ctx):
     eps = 3e-3
     As = [A.astype(np.float32) for A in _systems()[:5]]

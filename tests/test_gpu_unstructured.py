@@ -135,6 +135,60 @@ def test_sell16j_solve_equals_csr_and_oracle(gpu_ctx, monkeypatch, d20k, pre, dt
         assert it == it_o and np.linalg.norm(x - x_o) <= 1e-12 * np.linalg.norm(x_o)
 
 
+def _same_run(a, b):
+    return a[0] == b[0] and a[1] == b[1] and np.array_equal(a[2], b[2]) and np.array_equal(a[3], b[3])
+
+
+@pytest.mark.parametrize("reordered", [False, True])
+def test_graphs_follow_reinstalled_spai_on_sell16j(gpu_ctx, monkeypatch, d20k, reordered):
+    """Captured iteration graphs across set_spai on SELL-64J views (the smallest system here that
+    takes them; n = 20,000 > 2,560, so the graph path runs): solve with L, with a second L of the same
+    pattern, with L again -- the third solve repeats the first bit for bit (count, x, history) and the
+    second equals a fresh solver's.  `reordered`: the solver starts on the permuted system and the
+    dot order is switched to "openblas" and back between the solves, which rebuilds A's pattern
+    (the first switch returns to the unpermuted system for good).
+
+    These runs pin the bits across rebuilds.  They cannot make the allocator hand a rebuilt pattern
+    the addresses of the old one, so they do not by themselves prove that a stale graph is dropped:
+    that rests on graph_key taking every field of SellPattern (SellPattern::each_field)."""
+    A, m, _ = d20k
+    A = A.copy()
+    A.data = A.data.astype(np.float32).astype(np.float64)
+    assert A.shape[0] > 2560
+    Ls = []
+    for seed in (4, 5):
+        L = _cases.spai_like(A, seed=seed)
+        L.data = L.data.astype(np.float32).astype(np.float64)
+        Ls.append(L)
+    b = A @ np.asarray(m, dtype=np.float64).ravel()
+    monkeypatch.setenv("LSPCG_REORDER", "1" if reordered else "0")
+    s = _solver(A, Ls[0], "ext_spai")
+
+    def toggle():
+        if reordered:
+            s.set_dot_order("openblas", 1)
+            s.set_dot_order("compensated")
+
+    if reordered:
+        assert s.reorder_info["applied"]
+        first = _run(s, b, 1e-8, np.float64)  # on the permuted system; its graphs die with the switch
+        toggle()
+        assert not s.reorder_info["applied"]
+    assert all(v["columns"] == "sell16j" for v in s.views.values()), s.views
+    runs = [_run(s, b, 1e-8, np.float64)]
+    for L in (Ls[1], Ls[0]):
+        s.set_spai(L, 3e-3)
+        toggle()
+        runs.append(_run(s, b, 1e-8, np.float64))
+    assert runs[0][1] and runs[1][1]
+    assert _same_run(runs[2], runs[0])
+    assert not np.array_equal(runs[1][3], runs[0][3])  # the second factor was the one in use
+    monkeypatch.setenv("LSPCG_REORDER", "0")
+    assert _same_run(runs[1], _run(_solver(A, Ls[1], "ext_spai"), b, 1e-8, np.float64))
+    if reordered:  # the permuted system's solve: the same count, x to 1e-12 (other dot association)
+        assert first[0] == runs[0][0] and np.linalg.norm(first[2] - runs[0][2]) <= 1e-12 * np.linalg.norm(runs[0][2])
+
+
 def _banded_spd(n, spread, seed=0, long_tile=False):
     """Symmetric, strictly diagonally dominant (SPD) banded matrix with irregular rows (3..30 entries,
     columns within +-spread of the row): SELL-64 pads > 1.15, every 256-row tile reads

@@ -3,7 +3,8 @@ compiler flags, linked with the in-tree objects of the others (build/lspcg/*.o, 
 build first).  Measurement only: load it with LSPCG_LIB=<path> (tools/gnn_ab.py).
 
     python tools/build_variant.py exp/liblspcg_gs.so lspcg_gnn.hip -DLSPCG_GELU_SCALAR
-    python tools/build_variant.py tools/_variants/libx.so lspcg_pcg.hip,lspcg_core.hip -DX=1  (several units)
+    python tools/build_variant.py tools/_variants/libx.so lspcg_pcg.hip,lspcg_batch.hip -DX=1  (several units:
+        a flag read by a shared header, here the two solver units of lspcg_pcg_kernels.hpp)
 """
 import subprocess
 import sys
