@@ -11,10 +11,12 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/lspcg.h"
 
@@ -42,6 +44,33 @@ void set_error(const std::string& msg);
       return (code);                   \
     }                                  \
   } while (0)
+
+// hipMalloc'd scratch freed on scope exit.  keep(p) hands p to the caller (a longer-lived owner such
+// as a SellPattern field): scope exit no longer frees it.
+struct DevBuf {
+  std::vector<void*> p;
+  template <typename T>
+  int get(T** out, size_t count) {
+    void* v = nullptr;
+    LSPCG_HIP(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
+    p.push_back(v);
+    *out = static_cast<T*>(v);
+    return LSPCG_OK;
+  }
+  template <typename T>
+  T* keep(T* v) {
+    p.erase(std::remove(p.begin(), p.end(), static_cast<void*>(v)), p.end());
+    return v;
+  }
+  void release() {  // now, not at scope exit (a hipFree waits for the kernels enqueued before it)
+    for (void* v : p) (void)hipFree(v);
+    p.clear();
+  }
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+};
 
 // ---------------------------------------------------------------------------
 // Submission lock.  Independent solves may run on several host threads at once

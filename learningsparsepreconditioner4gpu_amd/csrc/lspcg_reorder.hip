@@ -482,23 +482,6 @@ __global__ void k_abs_offset_perm(int64_t nb, const int32_t* __restrict__ rowptr
   if ((threadIdx.x & 63) == 0 && acc) atomicAdd(sum, acc);
 }
 
-namespace {
-struct DevBuf {  // hipMalloc'd scratch freed on scope exit
-  std::vector<void*> p;
-  template <typename T>
-  int get(T** out, size_t count) {
-    void* v = nullptr;
-    LSPCG_HIP(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
-    p.push_back(v);
-    *out = static_cast<T*>(v);
-    return LSPCG_OK;
-  }
-  ~DevBuf() {
-    for (void* v : p) (void)hipFree(v);
-  }
-};
-}  // namespace
-
 constexpr int kRcmMaxComponents = 256;
 constexpr int kRcmMaxDegree = 1024;  // k_rcm_emit orders a parent's children in O(degree^2)
 constexpr int kRcmBatch = 16;        // BFS levels enqueued per host read-back

@@ -54,7 +54,8 @@ __global__ void __launch_bounds__(256) k_sell_fill(int64_t n, int64_t ns, const 
   }
 }
 
-// flag |= bit when some column is more than 32767 away from its slice's first row
+// flag |= bit when some column is more than 32767 away from its slice's first row: the bit says
+// that 16-bit offsets do NOT fit (the hosts' fits16 is its negation)
 __global__ void k_sell_fit16(int64_t n, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                              int* __restrict__ flag, int bit) {
   for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
@@ -435,131 +436,6 @@ __global__ void __launch_bounds__(256) k_xs_fill(int64_t n, int64_t ns, int64_t 
   }
 }
 
-static int slice_grid(int64_t ns) { return int(std::max<int64_t>(1, std::min<int64_t>(ns, 16384))); }
-
-// SELL-64X from a SELL-64J pattern (*taken = true when every tile touches <= kSellXMax blocks): the
-// column words are rewritten as LDS positions, the block lists added.
-static int xs_try(int64_t n, const int32_t* rowptr, const int32_t* colind, hipStream_t st, SellPattern* P,
-                  bool* taken) {
-  *taken = false;
-  const int64_t ntiles = (n + kSellWG - 1) / kSellWG;
-  int32_t *cnt = nullptr, *xlp = nullptr, *xl = nullptr;
-  int* flag = nullptr;
-  void* tmp = nullptr;
-  auto done = [&](hipError_t e) {
-    (void)hipFree(cnt);
-    (void)hipFree(xlp);
-    (void)hipFree(xl);
-    (void)hipFree(flag);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) {
-      set_error(std::string("sell_build_pattern (x-staged): ") + hipGetErrorString(e));
-      return LSPCG_ERR_HIP;
-    }
-    return LSPCG_OK;
-  };
-  int flag_h[4] = {1, 0, 0, 0};  // [over the limit, longest list, total, largest column]
-  hipError_t e = hipMalloc(&flag, 4 * sizeof(int));
-  if (e == hipSuccess) e = hipMemsetAsync(flag, 0, 4 * sizeof(int), st);
-  if (e == hipSuccess) e = hipMalloc(&cnt, sizeof(int32_t) * (ntiles + 1));
-  if (e == hipSuccess) e = hipMalloc(&xlp, sizeof(int32_t) * (ntiles + 1));
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (ntiles + 1), st);
-  const int grid = int(std::max<int64_t>(1, std::min<int64_t>(ntiles, 8192)));
-  if (e == hipSuccess) hipLaunchKernelGGL(k_xs_count, dim3(grid), dim3(256), 0, st, n, ntiles, rowptr, colind, cnt, flag);
-  size_t tb = 0;
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, xlp, int(ntiles + 1), st);
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 1);
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, xlp, int(ntiles + 1), st);
-  if (e == hipSuccess) e = hipMemcpyAsync(flag + 2, xlp + ntiles, sizeof(int), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(flag_h, flag, 4 * sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess || (flag_h[0] & 1)) return done(e);
-  e = hipMalloc(&xl, sizeof(int32_t) * std::max(flag_h[2], 1));
-  if (e == hipSuccess)
-    hipLaunchKernelGGL(k_xs_fill, dim3(grid), dim3(256), 0, st, n, P->ns, ntiles, rowptr, colind, xlp, P->gp, P->jc,
-                       P->lmap, xl, static_cast<int16_t*>(P->col));
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return done(e);
-  P->xlp = xlp;
-  P->xl = xl;
-  P->kx = flag_h[1];
-  P->xn = int64_t(flag_h[3]) + 1;
-  P->col_bits = kSellJagX;
-  xlp = nullptr;
-  xl = nullptr;
-  *taken = true;
-  return done(hipSuccess);
-}
-
-// SELL-64J pattern (P: the SELL-64 pattern with 16-bit offsets, already sized): *taken = true when
-// every row has <= 64 entries; P's gp becomes the element prefix, col the jagged 16-bit offsets.
-static int jag_try(int64_t n, const int32_t* rowptr, const int32_t* colind, hipStream_t st, SellPattern* P,
-                   bool* taken) {
-  *taken = false;
-  int32_t *etot = nullptr, *egp = nullptr;
-  uint8_t *lmap = nullptr, *jc = nullptr;
-  int16_t* col = nullptr;
-  int* flag = nullptr;
-  void* tmp = nullptr;
-  auto done = [&](hipError_t e) {
-    (void)hipFree(etot);
-    (void)hipFree(egp);
-    (void)hipFree(lmap);
-    (void)hipFree(jc);
-    (void)hipFree(col);
-    (void)hipFree(flag);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) {
-      set_error(std::string("sell_build_pattern (jagged): ") + hipGetErrorString(e));
-      return LSPCG_ERR_HIP;
-    }
-    return LSPCG_OK;
-  };
-  const int64_t ns = P->ns;
-  int flag_h[2] = {1, 0};
-  hipError_t e = hipMalloc(&flag, 2 * sizeof(int));
-  if (e == hipSuccess) e = hipMemsetAsync(flag, 0, 2 * sizeof(int), st);
-  if (e == hipSuccess) e = hipMalloc(&etot, sizeof(int32_t) * (ns + 1));
-  if (e == hipSuccess) e = hipMalloc(&egp, sizeof(int32_t) * (ns + 1));
-  if (e == hipSuccess) e = hipMalloc(&lmap, size_t(kSellC) * ns);
-  if (e == hipSuccess) e = hipMalloc(&jc, size_t(kSellJagMaxG) * ns);
-  if (e == hipSuccess) e = hipMemsetAsync(etot, 0, sizeof(int32_t) * (ns + 1), st);
-  if (e == hipSuccess)
-    hipLaunchKernelGGL(k_jag_meta, dim3(unsigned((ns + 3) / 4)), dim3(256), 0, st, n, ns, rowptr, lmap, jc, etot, flag);
-  size_t tb = 0;
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, etot, egp, int(ns + 1), st);
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 1);
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, etot, egp, int(ns + 1), st);
-  if (e == hipSuccess) e = hipMemcpyAsync(flag + 1, egp + ns, sizeof(int), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(flag_h, flag, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess || (flag_h[0] & 1)) return done(e);
-  const int64_t elems = flag_h[1];
-  e = hipMalloc(&col, sizeof(int16_t) * std::max<int64_t>(elems, 1));
-  if (e == hipSuccess)
-    hipLaunchKernelGGL((k_jag_fill<float, float>), dim3(slice_grid(ns)), dim3(256), 0, st, n, ns, egp, jc, lmap, rowptr,
-                       colind, static_cast<const float*>(nullptr), col, static_cast<float*>(nullptr));
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return done(e);
-  (void)hipFree(P->gp);
-  (void)hipFree(P->col);
-  P->gp = egp;
-  P->col = col;
-  P->lmap = lmap;
-  P->jc = jc;
-  P->elems = elems;
-  P->col_bits = kSellJag;
-  egp = nullptr;
-  col = nullptr;
-  lmap = nullptr;
-  jc = nullptr;
-  *taken = true;
-  return done(hipSuccess);
-}
-
-static int fill_grid(int64_t n) {
-  return int(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, kElemBlocksMax)));
-}
 
 // ---- BSELL-64 (BSR 3x3) ----------------------------------------------------------
 // block slots per row of each slice = its longest block row
@@ -629,380 +505,335 @@ __global__ void __launch_bounds__(256) k_bsdia_fill(int64_t nb, int64_t ns, cons
   }
 }
 
-int sell_build_pattern(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* colind, double max_pad,
-                       int cols, hipStream_t st, SellPattern* out);
+// ---- the view builder (host) -----------------------------------------------------------------
+// Scratch comes from a DevBuf and dies at scope exit; an array a layout keeps is handed to the
+// SellPattern with keep().  Every host wait of a build is a read_words() or an explicit
+// hipStreamSynchronize in this section.
+static int slice_grid(int64_t ns) { return int(std::max<int64_t>(1, std::min<int64_t>(ns, 16384))); }
+static int fill_grid(int64_t n) {
+  return int(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, kElemBlocksMax)));
+}
 
-// BSELL-DIA (allow_dia): the SELL-DIA dictionary / masks of the BLOCK graph (k_sdia_dict and
-// k_sdia_mask over the block rowptr / colind: offsets in block columns), taken when every slice has
-// <= 16 distinct block offsets and it stores at most 1/16 more block slots than BSELL-64
-static int bsdia_try(int64_t nb, const int32_t* rowptr, const int32_t* colind, hipStream_t st, SellPattern* P,
-                     bool* taken) {
-  *taken = false;
-  int32_t *cnt = nullptr, *dgp = nullptr, *dict = nullptr;
-  int* flag = nullptr;
-  void* tmp = nullptr;
-  uint16_t* mask = nullptr;
-  auto done = [&](hipError_t e) {
-    (void)hipFree(cnt);
-    (void)hipFree(tmp);
-    (void)hipFree(flag);
-    (void)hipFree(dgp);
-    (void)hipFree(dict);
-    (void)hipFree(mask);
-    if (e != hipSuccess) {
-      set_error(std::string("bsell_build_pattern (DIA): ") + hipGetErrorString(e));
-      return LSPCG_ERR_HIP;
-    }
+// The pattern under construction: released on scope exit unless commit() handed it to *out, so a
+// failed build leaves *out untouched and frees everything P owned.
+struct Building {
+  SellPattern P;
+  bool committed = false;
+  int commit(SellPattern* out) {
+    *out = P;
+    committed = true;
     return LSPCG_OK;
-  };
-  const int64_t ns = P->ns;
-  int flag_h[2] = {1, 0};
-  hipError_t e = hipMalloc(&flag, 2 * sizeof(int));
-  if (e == hipSuccess) e = hipMemsetAsync(flag, 0, 2 * sizeof(int), st);
-  if (e == hipSuccess) e = hipMalloc(&dict, sizeof(int32_t) * kSdiaMax * ns);
-  if (e == hipSuccess) e = hipMalloc(&cnt, sizeof(int32_t) * (ns + 1));
-  if (e == hipSuccess) e = hipMalloc(&dgp, sizeof(int32_t) * (ns + 1));
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (ns + 1), st);
-  if (e == hipSuccess)
-    hipLaunchKernelGGL(k_sdia_dict, dim3(unsigned((ns + 3) / 4)), dim3(256), 0, st, nb, ns, rowptr, colind, dict, cnt,
-                       flag);
+  }
+  ~Building() {
+    if (!committed) P.release();
+  }
+};
+
+template <typename T>
+static void replace(T*& slot, T* v) {  // slot = v, freeing the array it held
+  (void)hipFree(slot);
+  slot = v;
+}
+
+// prefix[0..m] = exclusive sum of cnt[0..m] (prefix[m]: the total), enqueued; the total also goes to
+// the device word *total_dev (a flag read fused with it) and / or to *total_host (valid after the
+// caller's wait) where given.
+static int scan_counts(int32_t* cnt, int32_t* prefix, int64_t m, DevBuf& B, hipStream_t st, int* total_dev,
+                       int32_t* total_host) {
   size_t tb = 0;
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, dgp, int(ns + 1), st);
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb);
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, dgp, int(ns + 1), st);
-  if (e == hipSuccess) e = hipMemcpyAsync(flag + 1, dgp + ns, sizeof(int), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(flag_h, flag, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return done(e);
-  // a slice whose distinct offsets outnumber its longest row pads a little more than BSELL-64
-  // (C4: 24,574 vs 24,572 slots); the column loads it drops are worth up to 1/16 more slots
-  if ((flag_h[0] & 1) || int64_t(flag_h[1]) > P->groups + P->groups / 16) return done(hipSuccess);
-  e = hipMalloc(&mask, sizeof(uint16_t) * kSellC * std::max<int64_t>(ns, 1));
-  if (e != hipSuccess) return done(e);
-  hipLaunchKernelGGL(k_sdia_mask, dim3(fill_grid(ns * kSellC)), dim3(kThreads), 0, st, nb, ns, rowptr, colind, dict, dgp,
-                     mask);
-  e = hipGetLastError();
-  if (e != hipSuccess) return done(e);
-  (void)hipFree(P->gp);
-  P->gp = dgp;
-  P->dict = dict;
-  P->col = mask;
+  void* tmp = nullptr;
+  LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, prefix, int(m + 1), st));  // size query
+  if (int rc = B.get(reinterpret_cast<uint8_t**>(&tmp), tb)) return rc;
+  LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, prefix, int(m + 1), st));
+  if (total_dev) LSPCG_HIP(hipMemcpyAsync(total_dev, prefix + m, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  if (total_host) LSPCG_HIP(hipMemcpyAsync(total_host, prefix + m, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  return LSPCG_OK;
+}
+
+// `count` device words to the host: a host wait
+static int read_words(int* host, const int* dev, int count, hipStream_t st) {
+  LSPCG_HIP(hipMemcpyAsync(host, dev, count * sizeof(int), hipMemcpyDeviceToHost, st));
+  LSPCG_HIP(hipStreamSynchronize(st));
+  return LSPCG_OK;
+}
+
+// Head of the scalar and the block build (P: n, nb, bs, ns, rowptr set): the slices' groups (bs 1) /
+// block slots (bs 3) per row, their prefix P->gp and total P->groups (one host wait), and whether
+// the padded slots exceed max_pad x nnz.
+static int build_head(int64_t nnz, double max_pad, hipStream_t st, SellPattern* P, bool* overpad) {
+  DevBuf B;
+  int32_t* cnt = nullptr;
+  int32_t groups = 0;
+  if (int rc = B.get(&cnt, P->ns + 1)) return rc;
+  LSPCG_HIP(hipMalloc(&P->gp, sizeof(int32_t) * (P->ns + 1)));
+  LSPCG_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (P->ns + 1), st));
+  const dim3 g(unsigned((P->ns + 3) / 4)), b(256);
+  if (P->ns && P->bs == 3) hipLaunchKernelGGL(k_bsell_len, g, b, 0, st, P->nb, P->ns, P->rowptr, cnt);
+  else if (P->ns) hipLaunchKernelGGL(k_sell_len, g, b, 0, st, P->nb, P->ns, P->rowptr, cnt);
+  if (int rc = scan_counts(cnt, P->gp, P->ns, B, st, nullptr, &groups)) return rc;
+  LSPCG_HIP(hipStreamSynchronize(st));
+  P->groups = groups;
+  *overpad = double(P->bs == 3 ? 64 : 256) * double(groups) > max_pad * double(std::max<int64_t>(nnz, 1));
+  return LSPCG_OK;
+}
+
+// SELL-DIA / BSELL-DIA attempt on P's row graph (k_sdia_dict and k_sdia_mask run on block rows and
+// block columns for bs 3), in two halves so that the caller fetches flag together with whatever else
+// it asked the device, in one host wait.  dia_enqueue: the slices' dictionaries, their sizes' prefix;
+// flag[0] |= 1 when there is no such layout (k_sdia_dict), flag[1] = its slot total.
+struct DiaScratch {
+  int32_t* dict = nullptr;
+  int32_t* gp = nullptr;
+};
+static int dia_enqueue(const SellPattern& P, const int32_t* colind, int* flag, DevBuf& B, hipStream_t st,
+                       DiaScratch* D) {
+  int32_t* cnt = nullptr;
+  if (int rc = B.get(&D->dict, kSdiaMax * P.ns) | B.get(&cnt, P.ns + 1) | B.get(&D->gp, P.ns + 1)) return rc;
+  LSPCG_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (P.ns + 1), st));
+  hipLaunchKernelGGL(k_sdia_dict, dim3(unsigned((P.ns + 3) / 4)), dim3(256), 0, st, P.nb, P.ns, P.rowptr, colind,
+                     D->dict, cnt, flag);
+  return scan_counts(cnt, D->gp, P.ns, B, st, flag + 1, nullptr);
+}
+// dia_try, with the host's copy of flag: *taken = true when the layout exists and stores at most
+// `budget` slots; P then holds it (gp, dict, groups, the row masks in col).  B is the attempt's scratch
+// (the caller's flag included): when taken it is freed here, before the mask kernel is enqueued, so
+// that no hipFree waits behind that kernel.
+static int dia_try(const int32_t* colind, const DiaScratch& D, const int* flag_h, int64_t budget, DevBuf& B,
+                   hipStream_t st, SellPattern* P, bool* taken) {
+  *taken = !(flag_h[0] & 1) && int64_t(flag_h[1]) <= budget;
+  if (!*taken) return LSPCG_OK;
+  replace(P->gp, B.keep(D.gp));
+  P->dict = B.keep(D.dict);
   P->groups = flag_h[1];
   P->col_bits = 1;
-  dgp = nullptr;
-  dict = nullptr;
-  mask = nullptr;
+  LSPCG_HIP(hipMalloc(&P->col, sizeof(uint16_t) * kSellC * std::max<int64_t>(P->ns, 1)));
+  B.release();
+  hipLaunchKernelGGL(k_sdia_mask, dim3(fill_grid(P->ns * kSellC)), dim3(kThreads), 0, st, P->nb, P->ns, P->rowptr, colind,
+                     P->dict, P->gp, static_cast<uint16_t*>(P->col));
+  LSPCG_HIP(hipGetLastError());
+  return LSPCG_OK;
+}
+
+// SELL-64C from the SELL-64 pattern (16-bit offsets fit): *taken = true when at least half of the
+// slots lie in slices of <= 64 distinct offsets.
+static int code_try(const int32_t* colind, hipStream_t st, SellPattern* P, bool* taken) {
+  *taken = false;
+  const int64_t ns = P->ns;
+  DevBuf B;
+  int32_t *dict = nullptr, *raw = nullptr, *rscan = nullptr;
+  int32_t rawg = 0;
+  if (int rc = B.get(&dict, kSellCodeMax * ns) | B.get(&raw, ns + 1) | B.get(&rscan, ns + 1)) return rc;
+  LSPCG_HIP(hipMemsetAsync(raw, 0, sizeof(int32_t) * (ns + 1), st));
+  hipLaunchKernelGGL(k_sellc_dict, dim3(unsigned((ns + 3) / 4)), dim3(256), 0, st, P->n, ns, P->rowptr, colind, P->gp,
+                     dict, raw);
+  if (int rc = scan_counts(raw, rscan, ns, B, st, nullptr, &rawg)) return rc;
+  LSPCG_HIP(hipStreamSynchronize(st));
+  if (int64_t(rawg) * 2 > P->groups) return LSPCG_OK;
+  P->dict = B.keep(dict);
+  LSPCG_HIP(hipMalloc(&P->rgp, sizeof(int32_t) * ns));
+  LSPCG_HIP(hipMalloc(&P->col, std::max<size_t>(size_t(256) * size_t(P->groups), 1)));
+  LSPCG_HIP(hipMalloc(&P->col2, sizeof(int16_t) * std::max<size_t>(size_t(256) * size_t(rawg), 1)));
+  hipLaunchKernelGGL(k_sellc_rgp, dim3(fill_grid(ns)), dim3(kThreads), 0, st, ns, raw, rscan, P->rgp);
+  hipLaunchKernelGGL(k_sellc_fill, dim3(slice_grid(ns)), dim3(256), 0, st, P->n, ns, P->gp, P->rowptr, colind, P->dict,
+                     P->rgp, static_cast<uint8_t*>(P->col), P->col2);
+  LSPCG_HIP(hipGetLastError());
+  LSPCG_HIP(hipStreamSynchronize(st));  // raw / rscan, which k_sellc_rgp reads, are freed on return
+  P->col_bits = 8;
   *taken = true;
-  return done(hipSuccess);
+  return LSPCG_OK;
+}
+
+// SELL-64J from the SELL-64 pattern (16-bit offsets fit): *taken = true when every row has <= 64
+// entries; P's gp becomes the element prefix, col the jagged 16-bit offsets.
+static int jag_try(const int32_t* colind, hipStream_t st, SellPattern* P, bool* taken) {
+  *taken = false;
+  const int64_t ns = P->ns;
+  DevBuf B;
+  int32_t *etot = nullptr, *egp = nullptr;
+  uint8_t *lmap = nullptr, *jc = nullptr;
+  int* flag = nullptr;
+  int flag_h[2] = {1, 0};  // [a row of more than 64 entries, stored entries]
+  if (int rc = B.get(&flag, 2) | B.get(&etot, ns + 1) | B.get(&egp, ns + 1) | B.get(&lmap, kSellC * ns) |
+               B.get(&jc, kSellJagMaxG * ns))
+    return rc;
+  LSPCG_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), st));
+  LSPCG_HIP(hipMemsetAsync(etot, 0, sizeof(int32_t) * (ns + 1), st));
+  hipLaunchKernelGGL(k_jag_meta, dim3(unsigned((ns + 3) / 4)), dim3(256), 0, st, P->n, ns, P->rowptr, lmap, jc, etot,
+                     flag);
+  if (int rc = scan_counts(etot, egp, ns, B, st, flag + 1, nullptr)) return rc;
+  if (int rc = read_words(flag_h, flag, 2, st)) return rc;
+  if (flag_h[0] & 1) return LSPCG_OK;
+  replace(P->gp, B.keep(egp));
+  P->lmap = B.keep(lmap);
+  P->jc = B.keep(jc);
+  P->elems = flag_h[1];
+  P->col_bits = kSellJag;
+  LSPCG_HIP(hipMalloc(&P->col, sizeof(int16_t) * std::max<int64_t>(P->elems, 1)));
+  hipLaunchKernelGGL((k_jag_fill<float, float>), dim3(slice_grid(ns)), dim3(256), 0, st, P->n, ns, P->gp, P->jc, P->lmap,
+                     P->rowptr, colind, static_cast<const float*>(nullptr), static_cast<int16_t*>(P->col),
+                     static_cast<float*>(nullptr));
+  LSPCG_HIP(hipGetLastError());
+  *taken = true;
+  return LSPCG_OK;
+}
+
+// SELL-64X from a SELL-64J pattern: *taken = true when every 256-row tile touches <= kSellXMax x
+// blocks; the column words are rewritten as LDS positions, the tiles' block lists added.
+static int xs_try(const int32_t* colind, hipStream_t st, SellPattern* P, bool* taken) {
+  *taken = false;
+  const int64_t n = P->n, ntiles = (n + kSellWG - 1) / kSellWG;
+  DevBuf B;
+  int32_t *cnt = nullptr, *xlp = nullptr;
+  int* flag = nullptr;
+  int flag_h[4] = {1, 0, 0, 0};  // [over the limit, longest list, total, largest column]
+  if (int rc = B.get(&flag, 4) | B.get(&cnt, ntiles + 1) | B.get(&xlp, ntiles + 1)) return rc;
+  LSPCG_HIP(hipMemsetAsync(flag, 0, 4 * sizeof(int), st));
+  LSPCG_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (ntiles + 1), st));
+  const int grid = int(std::max<int64_t>(1, std::min<int64_t>(ntiles, 8192)));
+  hipLaunchKernelGGL(k_xs_count, dim3(grid), dim3(256), 0, st, n, ntiles, P->rowptr, colind, cnt, flag);
+  if (int rc = scan_counts(cnt, xlp, ntiles, B, st, flag + 2, nullptr)) return rc;
+  if (int rc = read_words(flag_h, flag, 4, st)) return rc;
+  if (flag_h[0] & 1) return LSPCG_OK;
+  P->xlp = B.keep(xlp);
+  P->kx = flag_h[1];
+  P->xn = int64_t(flag_h[3]) + 1;
+  P->col_bits = kSellJagX;
+  LSPCG_HIP(hipMalloc(&P->xl, sizeof(int32_t) * std::max(flag_h[2], 1)));
+  hipLaunchKernelGGL(k_xs_fill, dim3(grid), dim3(256), 0, st, n, P->ns, ntiles, P->rowptr, colind, P->xlp, P->gp, P->jc,
+                     P->lmap, P->xl, static_cast<int16_t*>(P->col));
+  LSPCG_HIP(hipGetLastError());
+  *taken = true;
+  return LSPCG_OK;
+}
+
+// SELL-64 / BSELL-64 columns: 16-bit offsets from the slice's first row when they fit, else int32
+// columns.  The fill writes every slot, padding included.
+static int plain_columns(const int32_t* colind, bool fits16, hipStream_t st, SellPattern* P) {
+  P->col_bits = fits16 ? 16 : 32;
+  const int64_t slots = (P->bs == 3 ? 64 : 256) * P->groups;
+  LSPCG_HIP(hipMalloc(&P->col, size_t(P->col_bits / 8) * size_t(std::max<int64_t>(slots, 1))));
+  int32_t* c32 = fits16 ? nullptr : static_cast<int32_t*>(P->col);
+  int16_t* c16 = fits16 ? static_cast<int16_t*>(P->col) : nullptr;
+  const float* nosrc = nullptr;
+  float* nodst = nullptr;
+  const dim3 g(slice_grid(P->ns)), b(256);
+  if (P->ns && P->bs == 3)
+    hipLaunchKernelGGL((k_bsell_fill<float, float>), g, b, 0, st, P->nb, P->ns, P->gp, P->rowptr, colind, nosrc, c32, c16,
+                       nodst);
+  else if (P->ns)
+    hipLaunchKernelGGL((k_sell_fill<float, float>), g, b, 0, st, P->n, P->ns, P->gp, P->rowptr, colind, nosrc, c32, c16,
+                       nodst);
+  LSPCG_HIP(hipGetLastError());
+  return LSPCG_OK;
+}
+
+// The rule, top to bottom (lspcg_sell.hpp, above the declaration).  Host waits: the head, one read
+// of (SELL-DIA fits, its slot total, 16-bit offsets fit), then one or two per later attempt.
+int sell_build_pattern(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* colind, double max_pad,
+                       int cols, hipStream_t st, SellPattern* out) {
+  Building W;
+  SellPattern& P = W.P;
+  P.n = n;
+  P.nb = n;
+  P.ns = (n + kSellC - 1) / kSellC;
+  P.rowptr = rowptr;
+  bool overpad = false, taken = false;
+  if (int rc = build_head(nnz, max_pad, st, &P, &overpad)) return rc;
+  auto reject = [] {
+    set_error("sell: padding exceeds the limit (irregular row lengths)");
+    return LSPCG_ERR_UNSUPPORTED;
+  };
+  // padding past max_pad: only the jagged layout (which pads just each row's last group) may remain
+  if (overpad && !(cols & kSellColJag)) return reject();
+  if (overpad) cols &= ~(kSellColDia | kSellColCode);
+  bool fits16 = cols & kSellCol16;  // every column within 32767 of its slice's first row
+  if (n) {
+    DevBuf B;
+    DiaScratch D;
+    int* flag = nullptr;     // [bit 0: no SELL-DIA, bit 1: some offset beyond 16 bits | SELL-DIA slots]
+    int flag_h[2] = {1, 0};
+    if (int rc = B.get(&flag, 2)) return rc;
+    LSPCG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flag), (cols & kSellColDia) ? 0 : 1, 1, st));
+    LSPCG_HIP(hipMemsetAsync(flag + 1, 0, sizeof(int), st));
+    if (cols & kSellColDia)
+      if (int rc = dia_enqueue(P, colind, flag, B, st, &D)) return rc;
+    if (cols & kSellCol16)
+      hipLaunchKernelGGL(k_sell_fit16, dim3(fill_grid(n)), dim3(kThreads), 0, st, n, rowptr, colind, flag, 2);
+    if (int rc = read_words(flag_h, flag, 2, st)) return rc;
+    fits16 = fits16 && !(flag_h[0] & 2);
+    // SELL-DIA when it fits and stores no more slots than the 4-entry groups
+    if (int rc = dia_try(colind, D, flag_h, 4 * P.groups, B, st, &P, &taken)) return rc;
+    if (taken) return W.commit(out);
+  }
+  if ((cols & kSellColCode) && fits16 && n && P.groups > 0) {
+    if (int rc = code_try(colind, st, &P, &taken)) return rc;
+    if (taken) return W.commit(out);
+  }
+  // irregular row lengths: the jagged layout stores ~1.1 x nnz instead
+  if ((cols & kSellColJag) && fits16 && n && double(256) * double(P.groups) > kSellJagPad * double(nnz)) {
+    if (int rc = jag_try(colind, st, &P, &taken)) return rc;
+    if (taken && (cols & kSellColXs) && n >= kSellXMinN) {  // stage each tile's x blocks in LDS where they fit
+      bool xs = false;
+      if (int rc = xs_try(colind, st, &P, &xs)) return rc;
+    }
+    if (taken) return W.commit(out);
+  }
+  if (overpad) return reject();
+  if (int rc = plain_columns(colind, fits16, st, &P)) return rc;
+  return W.commit(out);
 }
 
 int bsell_build_pattern(int64_t nb, int64_t nnzb, const int32_t* rowptr, const int32_t* colind, double max_pad,
                         bool allow16, bool allow_dia, hipStream_t st, SellPattern* out) {
-  SellPattern P;
+  Building W;
+  SellPattern& P = W.P;
   P.n = 3 * nb;
   P.nb = nb;
   P.bs = 3;
   P.ns = (nb + kSellC - 1) / kSellC;
   P.rowptr = rowptr;
-  int32_t* cnt = nullptr;
-  void* tmp = nullptr;
-  auto fail = [&](hipError_t e) {
-    set_error(std::string("bsell_build_pattern: ") + hipGetErrorString(e));
-    (void)hipFree(cnt);
-    (void)hipFree(tmp);
-    P.release();
-    return LSPCG_ERR_HIP;
-  };
-  hipError_t e = hipMalloc(&cnt, sizeof(int32_t) * (P.ns + 1));
-  if (e == hipSuccess) e = hipMalloc(&P.gp, sizeof(int32_t) * (P.ns + 1));
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (P.ns + 1), st);
-  if (e != hipSuccess) return fail(e);
-  if (P.ns) hipLaunchKernelGGL(k_bsell_len, dim3(unsigned((P.ns + 3) / 4)), dim3(256), 0, st, nb, P.ns, rowptr, cnt);
-  size_t tb = 0;
-  e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, P.gp, int(P.ns + 1), st);
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb);
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, P.gp, int(P.ns + 1), st);
-  int32_t groups = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&groups, P.gp + P.ns, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(e);
-  (void)hipFree(cnt);
-  (void)hipFree(tmp);
-  cnt = nullptr;
-  tmp = nullptr;
-  P.groups = groups;
-  if (double(64) * double(groups) > max_pad * double(std::max<int64_t>(nnzb, 1))) {
-    P.release();
+  bool overpad = false, taken = false;
+  if (int rc = build_head(nnzb, max_pad, st, &P, &overpad)) return rc;
+  if (overpad) {
     set_error("bsell: padding exceeds the limit (irregular block-row lengths)");
     return LSPCG_ERR_UNSUPPORTED;
   }
   if (allow_dia && nb) {
-    bool taken = false;
-    if (int rc = bsdia_try(nb, rowptr, colind, st, &P, &taken)) {
-      P.release();
-      return rc;
-    }
-    if (taken) {
-      *out = P;
-      return LSPCG_OK;
-    }
-  }
-  int fit = 1;
-  if (allow16 && nb) {
+    DevBuf B;
+    DiaScratch D;
     int* flag = nullptr;
-    e = hipMalloc(&flag, sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), st);
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k_sell_fit16, dim3(fill_grid(nb)), dim3(kThreads), 0, st, nb, rowptr, colind, flag, 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(&fit, flag, sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(flag);
-    if (e != hipSuccess) return fail(e);
+    int flag_h[2] = {1, 0};  // [no BSELL-DIA, BSELL-DIA slots]
+    if (int rc = B.get(&flag, 2)) return rc;
+    LSPCG_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), st));
+    if (int rc = dia_enqueue(P, colind, flag, B, st, &D)) return rc;
+    if (int rc = read_words(flag_h, flag, 2, st)) return rc;
+    // a slice whose distinct offsets outnumber its longest row pads a little more than BSELL-64
+    // (C4: 24,574 vs 24,572 slots); the column loads it drops are worth up to 1/16 more slots
+    if (int rc = dia_try(colind, D, flag_h, P.groups + P.groups / 16, B, st, &P, &taken)) return rc;
+    if (taken) return W.commit(out);
   }
-  P.col_bits = fit == 0 ? 16 : 32;
-  e = hipMalloc(&P.col, size_t(P.col_bits / 8) * size_t(std::max<int64_t>(64 * P.groups, 1)));
-  if (e != hipSuccess) return fail(e);
-  if (P.ns)
-    hipLaunchKernelGGL((k_bsell_fill<float, float>), dim3(slice_grid(P.ns)), dim3(256), 0, st, nb, P.ns, P.gp, rowptr,
-                       colind, static_cast<const float*>(nullptr),
-                       P.col_bits == 32 ? static_cast<int32_t*>(P.col) : nullptr,
-                       P.col_bits == 16 ? static_cast<int16_t*>(P.col) : nullptr, static_cast<float*>(nullptr));
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(e);
-  *out = P;
-  return LSPCG_OK;
+  bool fits16 = false;  // every block column within 32767 of its slice's first block row
+  if (allow16 && nb) {
+    DevBuf B;
+    int* flag = nullptr;
+    int far = 1;
+    if (int rc = B.get(&flag, 1)) return rc;
+    LSPCG_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_sell_fit16, dim3(fill_grid(nb)), dim3(kThreads), 0, st, nb, rowptr, colind, flag, 1);
+    if (int rc = read_words(&far, flag, 1, st)) return rc;
+    fits16 = far == 0;
+  }
+  if (int rc = plain_columns(colind, fits16, st, &P)) return rc;
+  return W.commit(out);
 }
 
-int bsell_fill_values(const SellPattern& P, const void* src, int src_dtype, int dst_dtype, hipStream_t st, void** out) {
-  const size_t es = dst_dtype == LSPCG_F32 ? 4 : 8;
-  void* v = *out;  // an existing array of this pattern and dtype is refilled in place
-  const bool mine = v == nullptr;
-  if (!v) LSPCG_HIP(hipMalloc(&v, es * std::max<int64_t>(576 * P.groups, 1)));
-  const dim3 g(slice_grid(P.ns)), b(256);
-  const int32_t* nocol = nullptr;
-  if (P.ns && P.col_bits == 1) {
-    const auto* m = static_cast<const uint16_t*>(P.col);
-    if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F64)
-      hipLaunchKernelGGL((k_bsdia_fill<double, double>), g, b, 0, st, P.nb, P.ns, P.gp, m, P.rowptr,
-                         static_cast<const double*>(src), static_cast<double*>(v));
-    else if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_bsdia_fill<double, float>), g, b, 0, st, P.nb, P.ns, P.gp, m, P.rowptr,
-                         static_cast<const double*>(src), static_cast<float*>(v));
-    else if (src_dtype == LSPCG_F32 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_bsdia_fill<float, float>), g, b, 0, st, P.nb, P.ns, P.gp, m, P.rowptr,
-                         static_cast<const float*>(src), static_cast<float*>(v));
-    else
-      hipLaunchKernelGGL((k_bsdia_fill<float, double>), g, b, 0, st, P.nb, P.ns, P.gp, m, P.rowptr,
-                         static_cast<const float*>(src), static_cast<double*>(v));
-  } else if (P.ns) {
-    if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F64)
-      hipLaunchKernelGGL((k_bsell_fill<double, double>), g, b, 0, st, P.nb, P.ns, P.gp, P.rowptr, nocol,
-                         static_cast<const double*>(src), static_cast<int32_t*>(nullptr), static_cast<int16_t*>(nullptr),
-                         static_cast<double*>(v));
-    else if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_bsell_fill<double, float>), g, b, 0, st, P.nb, P.ns, P.gp, P.rowptr, nocol,
-                         static_cast<const double*>(src), static_cast<int32_t*>(nullptr), static_cast<int16_t*>(nullptr),
-                         static_cast<float*>(v));
-    else if (src_dtype == LSPCG_F32 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_bsell_fill<float, float>), g, b, 0, st, P.nb, P.ns, P.gp, P.rowptr, nocol,
-                         static_cast<const float*>(src), static_cast<int32_t*>(nullptr), static_cast<int16_t*>(nullptr),
-                         static_cast<float*>(v));
-    else
-      hipLaunchKernelGGL((k_bsell_fill<float, double>), g, b, 0, st, P.nb, P.ns, P.gp, P.rowptr, nocol,
-                         static_cast<const float*>(src), static_cast<int32_t*>(nullptr), static_cast<int16_t*>(nullptr),
-                         static_cast<double*>(v));
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    if (mine) (void)hipFree(v);
-    set_error(std::string("bsell_fill_values: ") + hipGetErrorString(e));
-    return LSPCG_ERR_HIP;
-  }
-  *out = v;
-  return LSPCG_OK;
-}
-
-int sell_build_pattern(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* colind, double max_pad,
-                       int cols, hipStream_t st, SellPattern* out) {
-  SellPattern P;
-  P.n = n;
-  P.nb = n;
-  P.ns = (n + kSellC - 1) / kSellC;
-  P.rowptr = rowptr;
-  int32_t* cnt = nullptr;
-  void* tmp = nullptr;
-  auto fail = [&](hipError_t e) {
-    set_error(std::string("sell_build_pattern: ") + hipGetErrorString(e));
-    (void)hipFree(cnt);
-    (void)hipFree(tmp);
-    P.release();
-    return LSPCG_ERR_HIP;
-  };
-  hipError_t e = hipMalloc(&cnt, sizeof(int32_t) * (P.ns + 1));
-  if (e == hipSuccess) e = hipMalloc(&P.gp, sizeof(int32_t) * (P.ns + 1));
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (P.ns + 1), st);
-  if (e != hipSuccess) return fail(e);
-  if (P.ns) hipLaunchKernelGGL(k_sell_len, dim3(unsigned((P.ns + 3) / 4)), dim3(256), 0, st, n, P.ns, rowptr, cnt);
-  size_t tb = 0;
-  e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, P.gp, int(P.ns + 1), st);
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb);
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, P.gp, int(P.ns + 1), st);
-  int32_t groups = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&groups, P.gp + P.ns, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(e);
-  (void)hipFree(cnt);
-  (void)hipFree(tmp);
-  cnt = nullptr;
-  tmp = nullptr;
-  P.groups = groups;
-  // padding past max_pad: only the jagged layout (which pads just each row's last group) may remain
-  const bool overpad = double(256) * double(groups) > max_pad * double(std::max<int64_t>(nnz, 1));
-  auto reject = [&]() {
-    P.release();
-    set_error("sell: padding exceeds the limit (irregular row lengths)");
-    return LSPCG_ERR_UNSUPPORTED;
-  };
-  if (overpad && !(cols & kSellColJag)) return reject();
-  if (overpad) cols &= ~(kSellColDia | kSellColCode);
-  // SELL-DIA: dictionaries and slot counts first; one host read of (flag, DIA slot total) decides
-  int fit16 = 0;  // 1 = some column out of 16-bit offset range
-  int flag_h[2] = {1, 0};  // [flags (bit 0: no SELL-DIA, bit 1: no 16-bit offsets), SELL-DIA slots]
-  int32_t* dgp = nullptr;  // DIA slot prefix
-  int* flag = nullptr;
-  if (n) {
-    e = hipMalloc(&flag, 2 * sizeof(int));
-    if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flag), (cols & kSellColDia) ? 0 : 1, 1, st);
-    if (e == hipSuccess) e = hipMemsetAsync(flag + 1, 0, sizeof(int), st);
-    if (e == hipSuccess && (cols & kSellColDia)) {
-      e = hipMalloc(&P.dict, sizeof(int32_t) * kSdiaMax * P.ns);
-      if (e == hipSuccess) e = hipMalloc(&cnt, sizeof(int32_t) * (P.ns + 1));
-      if (e == hipSuccess) e = hipMalloc(&dgp, sizeof(int32_t) * (P.ns + 1));
-      if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (P.ns + 1), st);
-      if (e == hipSuccess)
-        hipLaunchKernelGGL(k_sdia_dict, dim3(unsigned((P.ns + 3) / 4)), dim3(256), 0, st, n, P.ns, rowptr, colind, P.dict,
-                           cnt, flag);
-      size_t tb2 = 0;
-      if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, cnt, dgp, int(P.ns + 1), st);
-      if (e == hipSuccess) e = hipMalloc(&tmp, tb2);
-      if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb2, cnt, dgp, int(P.ns + 1), st);
-      if (e == hipSuccess) e = hipMemcpyAsync(flag + 1, dgp + P.ns, sizeof(int), hipMemcpyDeviceToDevice, st);
-    }
-    if (e == hipSuccess && (cols & kSellCol16))
-      hipLaunchKernelGGL(k_sell_fit16, dim3(fill_grid(n)), dim3(kThreads), 0, st, n, rowptr, colind, flag, 2);
-    if (e == hipSuccess) e = hipMemcpyAsync(flag_h, flag, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(cnt);
-    (void)hipFree(tmp);
-    cnt = nullptr;
-    tmp = nullptr;
-    if (e != hipSuccess) {
-      (void)hipFree(flag);
-      (void)hipFree(dgp);
-      return fail(e);
-    }
-    fit16 = (!(cols & kSellCol16) || (flag_h[0] & 2)) ? 1 : 0;
-  } else {
-    fit16 = (cols & kSellCol16) ? 0 : 1;
-  }
-  // SELL-DIA when it fits and stores no more slots than the 4-entry groups
-  const bool dia = n && !(flag_h[0] & 1) && int64_t(flag_h[1]) <= 4 * P.groups;
-  if (dia) {
-    (void)hipFree(P.gp);
-    P.gp = dgp;
-    dgp = nullptr;
-    P.groups = flag_h[1];
-    P.col_bits = 1;
-    e = hipMalloc(&P.col, sizeof(uint16_t) * kSellC * std::max<int64_t>(P.ns, 1));
-    (void)hipFree(flag);
-    if (e != hipSuccess) return fail(e);
-    hipLaunchKernelGGL(k_sdia_mask, dim3(fill_grid(P.ns * kSellC)), dim3(kThreads), 0, st, n, P.ns, rowptr, colind, P.dict,
-                       P.gp, static_cast<uint16_t*>(P.col));
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(e);
-    *out = P;
-    return LSPCG_OK;
-  }
-  (void)hipFree(flag);
-  (void)hipFree(dgp);
-  (void)hipFree(P.dict);
-  P.dict = nullptr;
-  if ((cols & kSellColCode) && !fit16 && n && P.groups > 0) {
-    // SELL-64C when at least half of the slots lie in slices of <= 64 distinct offsets
-    int32_t* raw = nullptr;
-    int32_t* rscan = nullptr;
-    int32_t rawg = 0;
-    e = hipMalloc(&P.dict, sizeof(int32_t) * kSellCodeMax * P.ns);
-    if (e == hipSuccess) e = hipMalloc(&raw, sizeof(int32_t) * (P.ns + 1));
-    if (e == hipSuccess) e = hipMalloc(&rscan, sizeof(int32_t) * (P.ns + 1));
-    if (e == hipSuccess) e = hipMemsetAsync(raw, 0, sizeof(int32_t) * (P.ns + 1), st);
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k_sellc_dict, dim3(unsigned((P.ns + 3) / 4)), dim3(256), 0, st, n, P.ns, rowptr, colind, P.gp,
-                         P.dict, raw);
-    size_t tb3 = 0;
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb3, raw, rscan, int(P.ns + 1), st);
-    if (e == hipSuccess) e = hipMalloc(&tmp, tb3 ? tb3 : 1);
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb3, raw, rscan, int(P.ns + 1), st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&rawg, rscan + P.ns, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(tmp);
-    tmp = nullptr;
-    if (e == hipSuccess && int64_t(rawg) * 2 <= P.groups) {
-      e = hipMalloc(&P.rgp, sizeof(int32_t) * P.ns);
-      if (e == hipSuccess) e = hipMalloc(&P.col, std::max<size_t>(size_t(256) * size_t(P.groups), 1));
-      if (e == hipSuccess) e = hipMalloc(&P.col2, sizeof(int16_t) * std::max<size_t>(size_t(256) * size_t(rawg), 1));
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sellc_rgp, dim3(fill_grid(P.ns)), dim3(kThreads), 0, st, P.ns, raw, rscan, P.rgp);
-        hipLaunchKernelGGL(k_sellc_fill, dim3(slice_grid(P.ns)), dim3(256), 0, st, n, P.ns, P.gp, rowptr, colind, P.dict,
-                           P.rgp, static_cast<uint8_t*>(P.col), P.col2);
-        e = hipGetLastError();
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(st);  // raw / rscan are freed below
-      (void)hipFree(raw);
-      (void)hipFree(rscan);
-      if (e != hipSuccess) return fail(e);
-      P.col_bits = 8;
-      *out = P;
-      return LSPCG_OK;
-    }
-    (void)hipFree(raw);
-    (void)hipFree(rscan);
-    (void)hipFree(P.dict);
-    P.dict = nullptr;
-    if (e != hipSuccess) return fail(e);
-  }
-  if ((cols & kSellColJag) && !fit16 && n && double(256) * double(P.groups) > kSellJagPad * double(nnz)) {
-    bool taken = false;  // irregular row lengths: the jagged layout stores ~1.1 x nnz instead
-    if (int rc = jag_try(n, rowptr, colind, st, &P, &taken)) {
-      P.release();
-      return rc;
-    }
-    if (taken && (cols & kSellColXs) && n >= kSellXMinN) {  // stage each tile's x blocks in LDS where they fit
-      bool xs = false;
-      if (int rc = xs_try(n, rowptr, colind, st, &P, &xs)) {
-        P.release();
-        return rc;
-      }
-    }
-    if (taken) {
-      *out = P;
-      return LSPCG_OK;
-    }
-  }
-  if (overpad) return reject();
-  P.col_bits = fit16 ? 32 : 16;
-  // the fill writes every slot (padding included)
-  const size_t cbytes = size_t(P.col_bits / 8) * size_t(std::max<int64_t>(256 * P.groups, 1));
-  e = hipMalloc(&P.col, cbytes);
-  if (e != hipSuccess) return fail(e);
-  if (P.ns)
-    hipLaunchKernelGGL((k_sell_fill<float, float>), dim3(slice_grid(P.ns)), dim3(256), 0, st, n, P.ns, P.gp, rowptr, colind,
-                       static_cast<const float*>(nullptr), P.col_bits == 32 ? static_cast<int32_t*>(P.col) : nullptr,
-                       P.col_bits == 16 ? static_cast<int16_t*>(P.col) : nullptr, static_cast<float*>(nullptr));
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(e);
-  *out = P;
-  return LSPCG_OK;
+// f(VS(), VD()) with the value types of (src_dtype, dst_dtype), each LSPCG_F32 or LSPCG_F64
+template <class F>
+static void with_value_types(int src_dtype, int dst_dtype, F f) {
+  if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F64) f(double(), double());
+  else if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F32) f(double(), float());
+  else if (src_dtype == LSPCG_F32 && dst_dtype == LSPCG_F32) f(float(), float());
+  else f(float(), double());
 }
 
 int sell_fill_values(const SellPattern& P, const int32_t* colind, const void* src, int src_dtype, int dst_dtype,
@@ -1012,48 +843,22 @@ int sell_fill_values(const SellPattern& P, const int32_t* colind, const void* sr
   const bool mine = v == nullptr;
   if (!v) LSPCG_HIP(hipMalloc(&v, es * std::max<int64_t>(P.slots(), 1)));
   const dim3 g(slice_grid(P.ns)), b(256);
-  if (P.ns && P.jagged()) {
-    int16_t* nc = nullptr;
-    if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F64)
-      hipLaunchKernelGGL((k_jag_fill<double, double>), g, b, 0, st, P.n, P.ns, P.gp, P.jc, P.lmap, P.rowptr, colind,
-                         static_cast<const double*>(src), nc, static_cast<double*>(v));
-    else if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_jag_fill<double, float>), g, b, 0, st, P.n, P.ns, P.gp, P.jc, P.lmap, P.rowptr, colind,
-                         static_cast<const double*>(src), nc, static_cast<float*>(v));
-    else if (src_dtype == LSPCG_F32 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_jag_fill<float, float>), g, b, 0, st, P.n, P.ns, P.gp, P.jc, P.lmap, P.rowptr, colind,
-                         static_cast<const float*>(src), nc, static_cast<float*>(v));
-    else
-      hipLaunchKernelGGL((k_jag_fill<float, double>), g, b, 0, st, P.n, P.ns, P.gp, P.jc, P.lmap, P.rowptr, colind,
-                         static_cast<const float*>(src), nc, static_cast<double*>(v));
-  } else if (P.ns && P.col_bits == 1) {
-    const auto* m = static_cast<const uint16_t*>(P.col);
-    if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F64)
-      hipLaunchKernelGGL((k_sdia_fill<double, double>), g, b, 0, st, P.n, P.ns, P.gp, m, P.rowptr,
-                         static_cast<const double*>(src), static_cast<double*>(v));
-    else if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_sdia_fill<double, float>), g, b, 0, st, P.n, P.ns, P.gp, m, P.rowptr,
-                         static_cast<const double*>(src), static_cast<float*>(v));
-    else if (src_dtype == LSPCG_F32 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_sdia_fill<float, float>), g, b, 0, st, P.n, P.ns, P.gp, m, P.rowptr,
-                         static_cast<const float*>(src), static_cast<float*>(v));
-    else
-      hipLaunchKernelGGL((k_sdia_fill<float, double>), g, b, 0, st, P.n, P.ns, P.gp, m, P.rowptr,
-                         static_cast<const float*>(src), static_cast<double*>(v));
-  } else if (P.ns) {
-    if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F64)
-      hipLaunchKernelGGL((k_sell_fill<double, double>), g, b, 0, st, P.n, P.ns, P.gp, P.rowptr, colind,
-                         static_cast<const double*>(src), static_cast<int32_t*>(nullptr), static_cast<int16_t*>(nullptr), static_cast<double*>(v));
-    else if (src_dtype == LSPCG_F64 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_sell_fill<double, float>), g, b, 0, st, P.n, P.ns, P.gp, P.rowptr, colind,
-                         static_cast<const double*>(src), static_cast<int32_t*>(nullptr), static_cast<int16_t*>(nullptr), static_cast<float*>(v));
-    else if (src_dtype == LSPCG_F32 && dst_dtype == LSPCG_F32)
-      hipLaunchKernelGGL((k_sell_fill<float, float>), g, b, 0, st, P.n, P.ns, P.gp, P.rowptr, colind,
-                         static_cast<const float*>(src), static_cast<int32_t*>(nullptr), static_cast<int16_t*>(nullptr), static_cast<float*>(v));
-    else
-      hipLaunchKernelGGL((k_sell_fill<float, double>), g, b, 0, st, P.n, P.ns, P.gp, P.rowptr, colind,
-                         static_cast<const float*>(src), static_cast<int32_t*>(nullptr), static_cast<int16_t*>(nullptr), static_cast<double*>(v));
-  }
+  if (P.ns)
+    with_value_types(src_dtype, dst_dtype, [&](auto vs, auto vd) {
+      using VS = decltype(vs);
+      using VD = decltype(vd);
+      const VS* s = static_cast<const VS*>(src);
+      VD* d = static_cast<VD*>(v);
+      int32_t* no32 = nullptr;
+      int16_t* no16 = nullptr;
+      if (P.jagged())
+        hipLaunchKernelGGL((k_jag_fill<VS, VD>), g, b, 0, st, P.n, P.ns, P.gp, P.jc, P.lmap, P.rowptr, colind, s, no16, d);
+      else if (P.col_bits == 1)
+        hipLaunchKernelGGL((k_sdia_fill<VS, VD>), g, b, 0, st, P.n, P.ns, P.gp, static_cast<const uint16_t*>(P.col),
+                           P.rowptr, s, d);
+      else
+        hipLaunchKernelGGL((k_sell_fill<VS, VD>), g, b, 0, st, P.n, P.ns, P.gp, P.rowptr, colind, s, no32, no16, d);
+    });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     if (mine) (void)hipFree(v);
@@ -1064,5 +869,35 @@ int sell_fill_values(const SellPattern& P, const int32_t* colind, const void* sr
   return LSPCG_OK;
 }
 
+int bsell_fill_values(const SellPattern& P, const void* src, int src_dtype, int dst_dtype, hipStream_t st, void** out) {
+  const size_t es = dst_dtype == LSPCG_F32 ? 4 : 8;
+  void* v = *out;  // an existing array of this pattern and dtype is refilled in place
+  const bool mine = v == nullptr;
+  if (!v) LSPCG_HIP(hipMalloc(&v, es * std::max<int64_t>(576 * P.groups, 1)));
+  const dim3 g(slice_grid(P.ns)), b(256);
+  if (P.ns)
+    with_value_types(src_dtype, dst_dtype, [&](auto vs, auto vd) {
+      using VS = decltype(vs);
+      using VD = decltype(vd);
+      const VS* s = static_cast<const VS*>(src);
+      VD* d = static_cast<VD*>(v);
+      const int32_t* nocol = nullptr;
+      int32_t* no32 = nullptr;
+      int16_t* no16 = nullptr;
+      if (P.col_bits == 1)
+        hipLaunchKernelGGL((k_bsdia_fill<VS, VD>), g, b, 0, st, P.nb, P.ns, P.gp, static_cast<const uint16_t*>(P.col),
+                           P.rowptr, s, d);
+      else
+        hipLaunchKernelGGL((k_bsell_fill<VS, VD>), g, b, 0, st, P.nb, P.ns, P.gp, P.rowptr, nocol, s, no32, no16, d);
+    });
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    if (mine) (void)hipFree(v);
+    set_error(std::string("bsell_fill_values: ") + hipGetErrorString(e));
+    return LSPCG_ERR_HIP;
+  }
+  *out = v;
+  return LSPCG_OK;
+}
 
 }  // namespace lspcg

@@ -886,11 +886,19 @@ namespace lspcg {
 // Host-side construction (lspcg_sell.hip), enqueued on `st`.
 // Builds the SELL-64 pattern of a scalar CSR (n rows); fails with LSPCG_ERR_UNSUPPORTED when the
 // padded size exceeds max_pad x nnz (irregular row lengths: the CSR kernel is used instead).
-// cols (kSellCol16 | kSellColDia | kSellColCode): the column storages allowed besides int32; SELL-DIA
-// is taken when every slice has <= 16 distinct offsets, every row is sorted and it stores no more
-// slots than the 4-entry groups would, else (kSellColCode, 16-bit offsets fit, rows sorted) SELL-64C
-// when at least half of the slots fall in slices of <= 64 distinct offsets, else 16-bit offsets
-// when they fit.
+// cols (kSellCol16 | kSellColDia | kSellColCode | kSellColJag | kSellColXs): the column storages
+// allowed besides int32.  The build tries them in this order, one function per layout (dia_try,
+// code_try, jag_try + xs_try, plain_columns), and takes the first that applies:
+//   SELL-DIA (kSellColDia) when every slice has <= 16 distinct offsets, every row is sorted and it
+//     stores no more slots than the 4-entry groups would;
+//   SELL-64C (kSellColCode, 16-bit offsets fit) when at least half of the slots fall in slices of
+//     <= 64 distinct offsets;
+//   SELL-64J (kSellColJag, 16-bit offsets fit) when SELL-64 would pad more than kSellJagPad x nnz and
+//     no row has more than 64 entries -- the only layout left past max_pad; SELL-64X on top of it
+//     (kSellColXs, n >= kSellXMinN) when every 256-row tile reads <= kSellXMax x blocks;
+//   16-bit offsets (kSellCol16) when they fit, else int32 columns.
+// Host waits: one for the group total, one for (SELL-DIA fits, its slot total, 16-bit offsets fit)
+// together, then one per later attempt (two for SELL-64C when taken).  On failure *out is untouched.
 int sell_build_pattern(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* colind, double max_pad,
                        int cols, hipStream_t st, SellPattern* out);
 // Allocates and fills the SELL value array of a CSR with the same pattern (*out == nullptr), or

@@ -314,6 +314,45 @@ def test_prepare_spmv_bsr3_keeps_bits(gpu_ctx, monkeypatch, dtype, case, bsdia):
     assert np.array_equal(y0, ref) and np.array_equal(y, ref), (case, kind)
 
 
+@pytest.mark.parametrize("bsdia", ["1", "0"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_prepare_spmv_bsr3_int32_block_columns(gpu_ctx, monkeypatch, dtype, bsdia):
+    """BSR 3x3 with block columns 35,000 block rows away: every slice has <= 3 block offsets, so
+    BSELL-DIA (kind 1) is taken where allowed; with LSPCG_BSDIA=0 the 16-bit block-column offsets do
+    not fit (35,000 > 32,767) and the BSELL-64 copy carries int32 columns (kind 32).  Both give the
+    staged block kernel's and scipy's bits."""
+    from learningsparsepreconditioner4gpu_amd.sparse import DeviceMatrix
+
+    monkeypatch.setenv("LSPCG_BSDIA", bsdia)
+    nb = 40000
+    I = np.arange(nb)
+    pat = sp.csr_matrix((np.ones(2 * nb), (np.r_[I, I], np.r_[I, (I + 35000) % nb])), shape=(nb, nb))
+    pat.sort_indices()
+    vals = np.random.default_rng(11).normal(size=(pat.nnz, 3, 3)).astype(dtype)
+    B = sp.bsr_matrix((vals, pat.indices, pat.indptr), shape=(3 * nb, 3 * nb))
+    x = np.random.default_rng(12).normal(size=B.shape[0]).astype(dtype)
+    ref = B @ x
+    Ad = DeviceMatrix.from_scipy(B, dtype=dtype, block_size=3)
+    y0 = Ad.matvec(torch.from_numpy(x).cuda()).cpu().numpy()  # staged block kernel
+    kind = Ad.prepare_spmv()
+    assert kind == (1 if bsdia == "1" else 32), kind
+    y = Ad.matvec(torch.from_numpy(x).cuda()).cpu().numpy()
+    assert np.array_equal(y0, ref) and np.array_equal(y, ref), kind
+
+
+@pytest.mark.parametrize("n", [5, 130])
+def test_prepare_spmv_pattern_without_entries(gpu_ctx, n):
+    """A matrix without a single stored entry: the analysis step keeps the CSR kernel and the
+    product is exactly zero."""
+    A = sp.csr_matrix((n, n), dtype=np.float64)
+    x = np.random.default_rng(13).normal(size=n)
+    Ad = _dm(A)
+    kind = Ad.prepare_spmv()
+    assert kind == 0  # the value the commit before the builder's restructuring returned, not _expected_kind's
+    y = Ad.matvec(torch.from_numpy(x).cuda()).cpu().numpy()
+    assert np.array_equal(y, np.zeros(n))
+
+
 def _offset_matrix(n, offsets, seed=0):
     """Banded matrix with the given row-relative offsets (clipped at the borders)."""
     rng = np.random.default_rng(seed)
