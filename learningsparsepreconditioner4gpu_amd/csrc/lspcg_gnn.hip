@@ -32,15 +32,12 @@
 
 #include "lspcg_internal.hpp"
 #include "lspcg_gnn.hpp"
+#include "lspcg_gnn_pack.hpp"
 
 namespace lspcg {
 
 constexpr int CE = 256;      // edges per LDS chunk (256 x 16 x 4 B = 16 KiB)
 constexpr int kMaxIn = 32;   // encoder input features supported
-
-// Fragment block of one FeedForward (floats): [A1 (S1 x 64) | C1 (64 x 4) | A2 (4 x 64) |
-// C2 (64 x 4) | A3 (4 x 64) | C3 (64 x 4)]
-__host__ __device__ constexpr int frag_size(int s1) { return s1 * 64 + 5 * 256; }
 
 // GELU(v) = v Phi(v) = max(v, 0) - |v| m(|v|),  m(a) = Phi(-a) = erfc(a / sqrt2) / 2 (either sign
 // of v; nn.GELU's exact-erf form).  log2 m(a) on [0, 5.75] is a degree-6 polynomial (fp32
@@ -196,17 +193,7 @@ __device__ __forceinline__ void ff2_48(const float* fa, const float* fb, const f
 using h4 = _Float16 __attribute__((ext_vector_type(4)));
 using hf2 = _Float16 __attribute__((ext_vector_type(2)));
 
-// f16 block of one FeedForward(48 -> 16 -> 16 -> out) (dwords, 64 lanes): [W1 hi, K block 0 / 1 / 2
-// (2 dwords = 4 halves per lane each) | W1 lo, blocks 0 / 1 / 2 | C1 (4 floats / lane) | W2 hi | W2 lo |
-// C2 | W3 hi | W3 lo | C3 | 2^-s1, 2^-s2, 2^-s3, pad].  Every product is a v_mfma_f32_16x16x16f16:
-// K slot (q, j) of block i is the lane's in[4i + j] (feature 16i + 4q + j, as feat48); C = 2^s b in
-// accumulator layout.  (v_mfma_f32_16x16x32_f16 -- one instruction for blocks 0 and 1 -- lost its
-// operands: hipcc reused its A / B registers for VALU results right after issue, and the products
-// went missing in the edge decoder; 16x16x16 has no such hazard gap.)
-constexpr int kH48 = 2052;
-constexpr int kH48W1h = 0, kH48W1l = 384, kH48C1 = 768;
-constexpr int kH48W2h = 1024, kH48W2l = 1152, kH48C2 = 1280, kH48W3h = 1536, kH48W3l = 1664, kH48C3 = 1792;
-constexpr int kH48S = 2048;
+// The split-f16 block layouts (kH48*, kH16*) are in lspcg_gnn_pack.hpp, beside the packer that writes them.
 
 // (a, b) -> packed f16 pairs hi = RNE(a, b), lo = RNE(a - hi, b - hi) (x - hi is exact in fp32).
 // The residuals come straight from the f16 halves: v_fma_mix_f32 reads src0 as f16 (lo or hi half
@@ -296,12 +283,7 @@ __device__ __forceinline__ void ff2_48(const float* fa, const float* fb, const f
   ob = layer16h(fb, kH48W3h, kH48W3l, kH48C3, 1.0f, xbh, xbl, lane);
 }
 
-// FeedForward(16 -> 16 -> 16 -> 16) (the node MLP) on split operands: block [W1 hi | W1 lo | C1 | W2 hi |
-// W2 lo | C2 | W3 hi | W3 lo | C3 | 2^-s1..3, pad | the encoder's magnitude bounds B1, c1, B2, c2
-// (ff1_16_enc)] (kH16 dwords; K slot (q, j) = the lane's in[j], i.e.
-// feature 4q + j, as feat16); us = its 2^-s factors
-constexpr int kH16 = 1548;
-constexpr int kH16S = 1536;
+// FeedForward(16 -> 16 -> 16 -> 16) (the node MLP) on split operands (kH16 block); us = its 2^-s factors
 __device__ __forceinline__ f4 ff1_16(const float* fa, const float (&in)[4], int lane, const float (&us)[3]) {
   h4 xh, xl;
   split4(in, xh, xl);
@@ -864,256 +846,30 @@ __global__ void __launch_bounds__(256, 4) k_mp_layer(int64_t N, const float* __r
   }
 }
 
-static int egrid(int64_t n) {
-  int64_t g = (n + kThreads - 1) / kThreads;
-  return int(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
-
 static int tgrid(int64_t items) {  // 64 items (4 waves x 16) per workgroup
   int64_t g = (items + 63) / 64;
   return int(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
+// the instance of a kernel for the handle's precision and descriptor
+using MpKernel = decltype(&k_mp_layer<false, 0>);
+static MpKernel mp_kernel(bool f32, int s1e) {  // s1e in 0..3 (0: the edge encoder is not fused in)
+  static constexpr MpKernel k[2][4] = {
+      {k_mp_layer<false, 0>, k_mp_layer<false, 1>, k_mp_layer<false, 2>, k_mp_layer<false, 3>},
+      {k_mp_layer<true, 0>, k_mp_layer<true, 1>, k_mp_layer<true, 2>, k_mp_layer<true, 3>}};
+  return k[f32][s1e];
+}
+template <typename IT>
+static auto dec_kernel(bool f32, int edge_out) {  // edge_out in {1, 4, 9} (lspcg_gnn_create)
+  static constexpr decltype(&k_edge_dec<false, 1, IT>) k[2][3] = {
+      {k_edge_dec<false, 1, IT>, k_edge_dec<false, 4, IT>, k_edge_dec<false, 9, IT>},
+      {k_edge_dec<true, 1, IT>, k_edge_dec<true, 4, IT>, k_edge_dec<true, 9, IT>}};
+  return k[f32][edge_out == 1 ? 0 : edge_out == 4 ? 1 : 2];
+}
+
 }  // namespace lspcg
 
 using namespace lspcg;
-
-// ---------------------------------------------------------------------------
-// Host-side fragment preparation
-// ---------------------------------------------------------------------------
-namespace {
-
-struct FF {  // views into the packed (reference-layout) blob
-  const float* W1;
-  const float* b1;
-  const float* W2;
-  const float* b2;
-  const float* W3;
-  const float* b3;
-  int in, out;
-};
-
-FF ff_at(const float* w, int in, int out) {
-  FF f;
-  f.in = in;
-  f.out = out;
-  f.W1 = w;
-  f.b1 = w + H * in;
-  f.W2 = f.b1 + H;
-  f.b2 = f.W2 + H * H;
-  f.W3 = f.b2 + H;
-  f.b3 = f.W3 + out * H;
-  return f;
-}
-
-// Append the fragment block of `f` (LayerNorm affine gamma/beta folded into layer 1 when given).
-// feat(s, q) = input feature in K slot q of step s (-1 = zero).
-template <class Feat>
-void emit_frag(std::vector<float>& o, const FF& f, int s1, Feat feat, const float* gamma, const float* beta) {
-  std::vector<double> W1(H * f.in), b1(H);
-  for (int i = 0; i < H; ++i) {
-    double bb = f.b1[i];
-    for (int k = 0; k < f.in; ++k) {
-      const double w = f.W1[i * f.in + k];
-      W1[i * f.in + k] = gamma ? w * gamma[k] : w;
-      if (beta) bb += w * beta[k];
-    }
-    b1[i] = bb;
-  }
-  for (int s = 0; s < s1; ++s)
-    for (int l = 0; l < 64; ++l) {
-      const int fi = feat(s, l >> 4);
-      o.push_back(fi >= 0 && fi < f.in ? float(W1[(l & 15) * f.in + fi]) : 0.f);
-    }
-  for (int l = 0; l < 64; ++l)
-    for (int r = 0; r < 4; ++r) o.push_back(float(b1[4 * (l >> 4) + r]));
-  for (int s = 0; s < 4; ++s)
-    for (int l = 0; l < 64; ++l) o.push_back(f.W2[(l & 15) * H + 4 * (l >> 4) + s]);
-  for (int l = 0; l < 64; ++l)
-    for (int r = 0; r < 4; ++r) o.push_back(f.b2[4 * (l >> 4) + r]);
-  for (int s = 0; s < 4; ++s)
-    for (int l = 0; l < 64; ++l) {
-      const int i = l & 15;
-      o.push_back(i < f.out ? f.W3[i * H + 4 * (l >> 4) + s] : 0.f);
-    }
-  for (int l = 0; l < 64; ++l)
-    for (int r = 0; r < 4; ++r) {
-      const int i = 4 * (l >> 4) + r;
-      o.push_back(i < f.out ? f.b3[i] : 0.f);
-    }
-}
-
-auto feat48 = [](int s, int q) { return (s >> 2) * 16 + 4 * q + (s & 3); };
-
-// The split-f16 block of a FeedForward(48 -> 16 -> 16 -> out) (ff2_48; layout at kH48): weights
-// scaled by 2^s per matrix (max |W| 2^s in [2^10, 2^11)), split into RNE f16 pairs.
-void emit_frag_h_any(std::vector<float>& o, const FF& f, const float* gamma, const float* beta, bool in48) {
-  std::vector<float> W1(H * f.in), b1(H);
-  for (int i = 0; i < H; ++i) {
-    double bb = f.b1[i];
-    for (int k = 0; k < f.in; ++k) {
-      const double w = f.W1[i * f.in + k];
-      W1[i * f.in + k] = float(gamma ? w * gamma[k] : w);
-      if (beta) bb += w * beta[k];
-    }
-    b1[i] = float(bb);
-  }
-  auto scale_exp = [](auto get, int rows, int cols) {
-    double mx = 0;
-    for (int i = 0; i < rows; ++i)
-      for (int k = 0; k < cols; ++k) mx = std::max(mx, std::fabs(double(get(i, k))));
-    if (mx == 0) return 0;
-    int e;
-    std::frexp(mx, &e);  // mx in [2^(e-1), 2^e)
-    return 11 - e;       // max |W| 2^s in [2^10, 2^11)
-  };
-  auto w1 = [&](int i, int k) { return k < f.in ? W1[i * f.in + k] : 0.f; };  // 16-slot blocks pad fin < 16
-  auto w2 = [&](int i, int k) { return f.W2[i * H + k]; };
-  auto w3 = [&](int i, int k) { return i < f.out ? f.W3[i * H + k] : 0.f; };
-  const int s1 = scale_exp(w1, H, f.in), s2 = scale_exp(w2, H, H), s3 = scale_exp(w3, H, H);
-  auto push_pairs = [&](auto get, int s, int per_lane, auto kidx, bool lo) {  // per lane: per_lane halves
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < per_lane; j += 2) {
-        unsigned u = 0;
-        for (int t = 0; t < 2; ++t) {
-          const int k = kidx(l >> 4, j + t);
-          const float x = k >= 0 ? std::ldexp(get(l & 15, k), s) : 0.f;
-          const _Float16 h = static_cast<_Float16>(x);
-          const _Float16 v = lo ? static_cast<_Float16>(x - static_cast<float>(h)) : h;
-          u |= unsigned(__builtin_bit_cast(unsigned short, v)) << (16 * t);
-        }
-        o.push_back(__builtin_bit_cast(float, u));
-      }
-  };
-  auto push_bias = [&](auto get, int s) {
-    for (int l = 0; l < 64; ++l)
-      for (int r = 0; r < 4; ++r) o.push_back(std::ldexp(get(4 * (l >> 4) + r), s));
-  };
-  auto kh = [](int q, int j) { return 4 * q + j; };  // 16-wide inputs / hidden layers
-  if (in48) {  // three K blocks of 16: block i, slot (q, j) = feature 16 i + 4 q + j = feat48(4 i + j, q)
-    for (bool lo : {false, true})
-      for (int i = 0; i < 3; ++i) push_pairs(w1, s1, 4, [i](int q, int j) { return feat48(4 * i + j, q); }, lo);
-  } else {  // 16 inputs: one 16x16x16 product, K slot (q, j) = feature 4q + j
-    push_pairs(w1, s1, 4, kh, false);
-    push_pairs(w1, s1, 4, kh, true);
-  }
-  push_bias([&](int i) { return b1[i]; }, s1);
-  push_pairs(w2, s2, 4, kh, false);
-  push_pairs(w2, s2, 4, kh, true);
-  push_bias([&](int i) { return f.b2[i]; }, s2);
-  push_pairs(w3, s3, 4, kh, false);
-  push_pairs(w3, s3, 4, kh, true);
-  push_bias([&](int i) { return i < f.out ? f.b3[i] : 0.f; }, s3);
-  for (int s : {s1, s2, s3}) o.push_back(std::ldexp(1.0f, -s));
-  o.push_back(0.f);
-  if (!in48) {  // magnitude bounds for ff1_16_enc: max row sum of |W|, max |bias| + GELU's 0.17
-    auto rowsum = [](auto get, int rows, int cols) {
-      double mx = 0;
-      for (int i = 0; i < rows; ++i) {
-        double r = 0;
-        for (int k = 0; k < cols; ++k) r += std::fabs(double(get(i, k)));
-        mx = std::max(mx, r);
-      }
-      return float(mx);
-    };
-    auto absmax = [](auto get, int n) {
-      double mx = 0;
-      for (int i = 0; i < n; ++i) mx = std::max(mx, std::fabs(double(get(i))));
-      return float(mx + 0.17);
-    };
-    const float B1 = rowsum(w1, H, f.in), c1 = absmax([&](int i) { return b1[i]; }, H);
-    const float B2 = rowsum(w2, H, H), c2 = absmax([&](int i) { return f.b2[i]; }, H);
-    o.push_back(B1);
-    o.push_back(c1);
-    o.push_back(B2);
-    o.push_back(c2);
-    // the largest edge maximum m with max(B1 m + c1, B2 (B1 m + c1) + c2) < 2^14 (no hidden scale);
-    // half the device threshold, so the float rounding of the bounds cannot matter
-    const double lim = 16384.0, h1 = std::min(lim, (lim - c2) / std::max(double(B2), 1e-30));
-    const double ms = (h1 - c1) / std::max(double(B1), 1e-30);
-    o.push_back(float(std::max(0.0, ms)));
-    o.push_back(0.f);
-    o.push_back(0.f);
-    o.push_back(0.f);
-  }
-}
-// Largest |hidden activation| a LayerNorm-fed FeedForward can produce: LayerNorm outputs are at most
-// sqrt(n - 1) in magnitude (gamma / beta folded into layer 1), |GELU(z)| <= max(|z|, 0.17), so
-// |h1| <= ||W1'||_inf sqrt(n - 1) + max |b1'| + 0.17 and |h2| <= ||W2||_inf |h1| + max |b2| + 0.17.
-// The split-f16 products need it below 2^15 (f16 holds 65504): gnn_create runs the fp32-MFMA
-// kernels for weights past it.
-double ln_ff_hidden_bound(const FF& f, const float* gamma, const float* beta) {
-  double h1 = 0, h2 = 0, b2 = 0;
-  for (int i = 0; i < H; ++i) {
-    double r = 0, bb = f.b1[i];
-    for (int k = 0; k < f.in; ++k) {
-      r += std::fabs(double(f.W1[i * f.in + k]) * gamma[k]);
-      bb += double(f.W1[i * f.in + k]) * beta[k];
-    }
-    h1 = std::max(h1, r * std::sqrt(double(f.in - 1)) + std::fabs(bb) + 0.17);
-  }
-  for (int i = 0; i < H; ++i) {
-    double r = 0;
-    for (int k = 0; k < H; ++k) r += std::fabs(double(f.W2[i * H + k]));
-    h2 = std::max(h2, r);
-    b2 = std::max(b2, std::fabs(double(f.b2[i])));
-  }
-  return std::max(h1, h2 * h1 + b2 + 0.17);
-}
-// The split-f16 GEMMs carry each layer's result scaled by 2^s (s: emit_frag_h_any's exponent, max |W|
-// 2^s in [2^10, 2^11)); the last layer's messages are summed over a node's edges while still scaled.
-// A matrix of tiny weights beside O(1) biases (2^s large, the bias scaled alike) could push those
-// scaled values past fp32's range, which the per-message unscale never reached.  Returns
-// the largest scaled magnitude, 2^s x (|W| row bound x input bound + max |bias|), over the three
-// layers; gnn_create runs the fp32-MFMA kernels (no scaling) when it exceeds 2^96, which leaves 2^32
-// for a node's message sum.  (Seeded / trained weights: ~2^20.)
-double ln_ff_scaled_bound(const FF& f, const float* gamma, const float* beta) {
-  auto sexp = [](double mx) {
-    if (mx == 0) return 0;
-    int e;
-    std::frexp(mx, &e);
-    return 11 - e;
-  };
-  double w1 = 0, w2 = 0, w3 = 0, r1 = 0, r2 = 0, r3 = 0, b1 = 0, b2 = 0, b3 = 0;
-  for (int i = 0; i < H; ++i) {
-    double r = 0, bb = f.b1[i];
-    for (int k = 0; k < f.in; ++k) {
-      const double w = double(f.W1[i * f.in + k]) * gamma[k];
-      w1 = std::max(w1, std::fabs(w));
-      r += std::fabs(w);
-      bb += double(f.W1[i * f.in + k]) * beta[k];
-    }
-    r1 = std::max(r1, r);
-    b1 = std::max(b1, std::fabs(bb));
-    double q2 = 0, q3 = 0;
-    for (int k = 0; k < H; ++k) {
-      w2 = std::max(w2, std::fabs(double(f.W2[i * H + k])));
-      q2 += std::fabs(double(f.W2[i * H + k]));
-      if (i < f.out) {
-        w3 = std::max(w3, std::fabs(double(f.W3[i * H + k])));
-        q3 += std::fabs(double(f.W3[i * H + k]));
-      }
-    }
-    r2 = std::max(r2, q2);
-    r3 = std::max(r3, q3);
-    b2 = std::max(b2, std::fabs(double(f.b2[i])));
-    if (i < f.out) b3 = std::max(b3, std::fabs(double(f.b3[i])));
-  }
-  const double x1 = std::sqrt(double(f.in - 1));            // LayerNorm output bound
-  const double h1 = r1 * x1 + b1 + 0.17, h2 = r2 * h1 + b2 + 0.17;  // GELU outputs
-  return std::max({std::ldexp(r1 * x1 + b1, sexp(w1)), std::ldexp(r2 * h1 + b2, sexp(w2)),
-                   std::ldexp(r3 * h2 + b3, sexp(w3))});
-}
-void emit_frag_h(std::vector<float>& o, const FF& f, const float* gamma, const float* beta) {
-  emit_frag_h_any(o, f, gamma, beta, true);  // kH48 dwords
-}
-void emit_frag_h16(std::vector<float>& o, const FF& f, const float* gamma, const float* beta) {
-  emit_frag_h_any(o, f, gamma, beta, false);  // kH16 dwords
-}
-auto feat16 = [](int s, int q) { return 4 * q + s; };
-auto featenc = [](int s, int q) { return 4 * s + q; };
-
-}  // namespace
 
 static void gnn_free_ws(lspcg_gnn* g) {
   for (void* p : {(void*)g->xa, (void*)g->xb, (void*)g->ecsc, (void*)g->ptr, (void*)g->cnt, (void*)g->perm, (void*)g->inv,
@@ -1153,75 +909,22 @@ static int gnn_reserve(lspcg_gnn* g, int64_t N, int64_t E) {
 
 extern "C" {
 
-// Host side of lspcg_gnn_create / lspcg_gnn_set_weights: decides f32 / hidden_bound from the
-// weights, emits the fragment blob and uploads it with the weights themselves (the backward works
-// from the unfolded values).  Work queued on the handle's stream may still read the old fragments,
-// so the stream is drained first.
+// Host side of lspcg_gnn_create / lspcg_gnn_set_weights: packs the fragment blob (pack_fragments
+// decides f32 / hidden_bound from the weights) and uploads it with the weights themselves (the
+// backward works from the unfolded values).  Work queued on the handle's stream may still read the
+// old fragments, so the stream is drained first.
 static int gnn_load_weights(lspcg_gnn* g, const float* weights) {
-  const lspcg_gnn_desc& d = g->d;
   const int64_t need = g->nweights;
   std::vector<float> w(need);
   LSPCG_HIP(hipStreamSynchronize(g->ctx->stream));
   LSPCG_HIP(hipMemcpy(w.data(), weights, sizeof(float) * need, hipMemcpyDefault));  // host or device source
-  g->hidden_bound = 0;
-  g->o_layer.clear();
-  // precision: the split-f16 GEMMs hold hidden activations below 2^15; weights whose LayerNorm-fed
-  // MLPs could exceed that run the exact fp32-MFMA kernels instead (same results to ~1e-7, 1.2x slower)
-  {
-    int64_t ob = ff_size(d.node_in, H) + ff_size(d.edge_in, H);
-    double scaled = 0;  // ln_ff_scaled_bound over the layers
-    for (int l = 0; l < d.num_mp_layers; ++l) {
-      const float* node = w.data() + ob;
-      const float* edge = node + 2 * H + ff_size(H, H);
-      const float* msgp = edge + 6 * H + ff_size(3 * H, H);
-      ob += 2 * H + ff_size(H, H) + 2 * (6 * H + ff_size(3 * H, H));
-      g->hidden_bound = std::max({g->hidden_bound, ln_ff_hidden_bound(ff_at(msgp + 6 * H, 3 * H, H), msgp, msgp + 3 * H),
-                                  ln_ff_hidden_bound(ff_at(edge + 6 * H, 3 * H, H), edge, edge + 3 * H),
-                                  ln_ff_hidden_bound(ff_at(node + 2 * H, H, H), node, node + H)});
-      scaled = std::max({scaled, ln_ff_scaled_bound(ff_at(msgp + 6 * H, 3 * H, H), msgp, msgp + 3 * H),
-                         ln_ff_scaled_bound(ff_at(edge + 6 * H, 3 * H, H), edge, edge + 3 * H),
-                         ln_ff_scaled_bound(ff_at(node + 2 * H, H, H), node, node + H)});
-    }
-    const char* ev = std::getenv("LSPCG_GNN_F32");
-    g->f32 = !(g->hidden_bound < 32768.0) || !(scaled <= std::ldexp(1.0, 96)) || (ev && ev[0] == '1');
-  }
-  const bool f32 = g->f32;
-  std::vector<float> fr;
-  int64_t o = 0;
-  g->o_node_enc = int64_t(fr.size());
-  emit_frag(fr, ff_at(w.data() + o, d.node_in, H), (d.node_in + 3) / 4, featenc, nullptr, nullptr);
-  o += ff_size(d.node_in, H);
-  g->o_edge_enc = int64_t(fr.size());
-  emit_frag(fr, ff_at(w.data() + o, d.edge_in, H), (d.edge_in + 3) / 4, featenc, nullptr, nullptr);
-  const float* enc_w = w.data() + o;
-  o += ff_size(d.edge_in, H);
-  for (int l = 0; l < d.num_mp_layers; ++l) {
-    const float* node = w.data() + o;  // [ln_g 16 | ln_b 16 | FF(16->16)]
-    o += 2 * H + ff_size(H, H);
-    const float* edge = w.data() + o;  // [ln_g 48 | ln_b 48 | FF(48->16)]
-    o += 6 * H + ff_size(3 * H, H);
-    const float* msgp = w.data() + o;
-    o += 6 * H + ff_size(3 * H, H);
-    g->o_layer.push_back(int64_t(fr.size()));
-    if (f32) {
-      emit_frag(fr, ff_at(msgp + 6 * H, 3 * H, H), 12, feat48, msgp, msgp + 3 * H);
-      emit_frag(fr, ff_at(edge + 6 * H, 3 * H, H), 12, feat48, edge, edge + 3 * H);
-      emit_frag(fr, ff_at(node + 2 * H, H, H), 4, feat16, node, node + H);
-    } else {
-      emit_frag_h(fr, ff_at(msgp + 6 * H, 3 * H, H), msgp, msgp + 3 * H);
-      emit_frag_h(fr, ff_at(edge + 6 * H, 3 * H, H), edge, edge + 3 * H);
-      emit_frag_h16(fr, ff_at(node + 2 * H, H, H), node, node + H);
-    }
-  }
-  g->o_dec = int64_t(fr.size());
-  g->o_edge_enc_h = 0;
-  if (f32) {
-    emit_frag(fr, ff_at(w.data() + o, 3 * H, d.edge_out), 12, feat48, nullptr, nullptr);
-  } else {
-    emit_frag_h(fr, ff_at(w.data() + o, 3 * H, d.edge_out), nullptr, nullptr);
-    g->o_edge_enc_h = int64_t(fr.size());
-    if (d.edge_in <= 16) emit_frag_h16(fr, ff_at(enc_w, d.edge_in, H), nullptr, nullptr);
-  }
+  const char* ev = std::getenv("LSPCG_GNN_F32");
+  Fragments p;
+  if (int rc = pack_fragments(g->d, w, ev && ev[0] == '1', &p)) return rc;
+  const std::vector<float>& fr = p.blob;
+  g->o = std::move(p.o);
+  g->f32 = p.f32;
+  g->hidden_bound = p.hidden_bound;
   if (int64_t(fr.size()) > g->frag_cap) {  // the fp32 and the split-f16 blobs differ in size
     (void)hipFree(g->frag);
     g->frag = nullptr;
@@ -1292,22 +995,19 @@ int lspcg_gnn_build_csc(lspcg_gnn* g, int64_t N, int64_t E, const int64_t* edge_
   LSPCG_HIP(hipMemsetAsync(g->flag, 0, sizeof(int), st));
   // unsorted input leaves row starts unwritten (flagged): zeroed, k_csc_sym's searches stay in range
   LSPCG_HIP(hipMemsetAsync(g->ptr, 0, sizeof(int32_t) * (N + 1), st));
-  hipLaunchKernelGGL(k_csc_rowstart, dim3(egrid(E + 1)), dim3(kThreads), 0, st, N, E, edge_index, g->ptr,
-                     g->flag);
-  hipLaunchKernelGGL(k_csc_sym, dim3(egrid(E)), dim3(kThreads), 0, st, E, edge_index, g->ptr, g->perm, g->src, g->dst,
-                     g->flag);
+  launch(k_csc_rowstart, dim3(egrid(E + 1)), dim3(kThreads), st, N, E, edge_index, g->ptr, g->flag);
+  launch(k_csc_sym, dim3(egrid(E)), dim3(kThreads), st, E, edge_index, g->ptr, g->perm, g->src, g->dst, g->flag);
   int hflag = 0;
   LSPCG_HIP(hipMemcpyAsync(&hflag, g->flag, sizeof(int), hipMemcpyDeviceToHost, st));
   LSPCG_HIP(hipStreamSynchronize(st));
   if (hflag) {  // generic: count by dst, scan, slot fill, per-node sort by edge id
     LSPCG_HIP(hipMemsetAsync(g->cnt, 0, sizeof(int32_t) * (N + 1), st));
-    hipLaunchKernelGGL(k_csc_count, dim3(egrid(E)), dim3(kThreads), 0, st, E, edge_index, g->cnt);
+    launch(k_csc_count, dim3(egrid(E)), dim3(kThreads), st, E, edge_index, g->cnt);
     size_t tb = g->scan_bytes;
     LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(g->scan_tmp, tb, g->cnt, g->ptr, int(N + 1), st));
     LSPCG_HIP(hipMemsetAsync(g->cnt, 0, sizeof(int32_t) * (N + 1), st));
-    hipLaunchKernelGGL(k_csc_fill, dim3(egrid(E)), dim3(kThreads), 0, st, E, edge_index, g->ptr, g->cnt, g->perm);
-    hipLaunchKernelGGL(k_csc_sort, dim3(egrid(N)), dim3(kThreads), 0, st, N, edge_index, E, g->ptr, g->perm, g->inv,
-                       g->src, g->dst);
+    launch(k_csc_fill, dim3(egrid(E)), dim3(kThreads), st, E, edge_index, g->ptr, g->cnt, g->perm);
+    launch(k_csc_sort, dim3(egrid(N)), dim3(kThreads), st, N, edge_index, E, g->ptr, g->perm, g->inv, g->src, g->dst);
   }
   LSPCG_HIP(hipGetLastError());
   g->gei = edge_index;
@@ -1342,57 +1042,34 @@ int lspcg_gnn_forward(lspcg_gnn* g, int64_t N, int64_t E, const float* x, const 
   const int hflag = g->gflag;
   const int32_t* inv = hflag ? g->inv : g->perm;  // edge -> CSC slot (the involution is its own inverse)
   // encoders (the edge encoder is fused into the first layer when there is one and edge_in <= 12)
-  hipLaunchKernelGGL(k_encode<false>, dim3(tgrid(N)), dim3(256), 0, st, N, d.node_in, g->frag + g->o_node_enc, x,
-                     static_cast<const int32_t*>(nullptr), g->xa);
+  launch(k_encode<false>, dim3(tgrid(N)), dim3(256), st, N, d.node_in, g->frag + g->o.node_enc, x, nullptr, g->xa);
   const int s1e = (d.edge_in + 3) / 4;
   const bool fuse_enc = d.num_mp_layers > 0 && s1e <= 3;
   if (!fuse_enc)
-    hipLaunchKernelGGL(k_encode<true>, dim3(tgrid(E)), dim3(256), 0, st, E, d.edge_in, g->frag + g->o_edge_enc,
-                       edge_attr, g->perm, g->ecsc);
+    launch(k_encode<true>, dim3(tgrid(E)), dim3(256), st, E, d.edge_in, g->frag + g->o.edge_enc, edge_attr, g->perm,
+           g->ecsc);
   // message passing
   float* xc = g->xa;
   float* xn = g->xb;
   const unsigned lg = unsigned((N + 255) / 256);
   // the fused copy reads the split-f16 block (f32: the f32 fragments, held in registers)
-  const float* fenc = g->frag + (g->f32 ? g->o_edge_enc : g->o_edge_enc_h);
+  const float* fenc = g->frag + (g->f32 ? g->o.edge_enc : g->o.edge_enc_h);
   for (int l = 0; l < d.num_mp_layers; ++l) {
-    const int se = (l == 0 && fuse_enc) ? s1e : 0;
-    auto kern = g->f32 ? (se == 1   ? k_mp_layer<true, 1>
-                          : se == 2 ? k_mp_layer<true, 2>
-                          : se == 3 ? k_mp_layer<true, 3>
-                                    : k_mp_layer<true, 0>)
-                       : (se == 1   ? k_mp_layer<false, 1>
-                          : se == 2 ? k_mp_layer<false, 2>
-                          : se == 3 ? k_mp_layer<false, 3>
-                                    : k_mp_layer<false, 0>);
-    hipLaunchKernelGGL(kern, dim3(lg), dim3(256), 0, st, N, g->frag + g->o_layer[l], d.node_residual, d.edge_residual,
-                       g->ptr, g->src, g->dst, xc, g->ecsc, xn, fenc, d.edge_in, edge_attr,
-                       static_cast<const int32_t*>(g->perm));
+    launch(mp_kernel(g->f32, l == 0 && fuse_enc ? s1e : 0), dim3(lg), dim3(256), st, N, g->frag + g->o.layer[l],
+           d.node_residual, d.edge_residual, g->ptr, g->src, g->dst, xc, g->ecsc, xn, fenc, d.edge_in, edge_attr,
+           g->perm);
     std::swap(xc, xn);
   }
   // decoder
-  const float* fd = g->frag + g->o_dec;
+  const float* fd = g->frag + g->o.dec;
   // endpoints in edge order: the symmetric fast path's int32 dst / src are exactly edge_index's
   // rows (k_csc_sym: slot e's endpoints are (ei[E+e], ei[e])), half the index bytes of the int64 rows
-  if (!hflag) {
-    auto dec = g->f32 ? (d.edge_out == 1   ? k_edge_dec<true, 1, int32_t>
-                         : d.edge_out == 4 ? k_edge_dec<true, 4, int32_t>
-                                           : k_edge_dec<true, 9, int32_t>)
-                      : (d.edge_out == 1   ? k_edge_dec<false, 1, int32_t>
-                         : d.edge_out == 4 ? k_edge_dec<false, 4, int32_t>
-                                           : k_edge_dec<false, 9, int32_t>);
-    hipLaunchKernelGGL(dec, dim3(tgrid(E)), dim3(256), 0, st, E, fd, static_cast<const int32_t*>(g->dst),
-                       static_cast<const int32_t*>(g->src), inv, g->ecsc, xc, out);
-  } else {
-    auto dec = g->f32 ? (d.edge_out == 1   ? k_edge_dec<true, 1, int64_t>
-                         : d.edge_out == 4 ? k_edge_dec<true, 4, int64_t>
-                                           : k_edge_dec<true, 9, int64_t>)
-                      : (d.edge_out == 1   ? k_edge_dec<false, 1, int64_t>
-                         : d.edge_out == 4 ? k_edge_dec<false, 4, int64_t>
-                                           : k_edge_dec<false, 9, int64_t>);
-    hipLaunchKernelGGL(dec, dim3(tgrid(E)), dim3(256), 0, st, E, fd, edge_index, edge_index + E, inv, g->ecsc, xc,
-                       out);
-  }
+  if (!hflag)
+    launch(dec_kernel<int32_t>(g->f32, d.edge_out), dim3(tgrid(E)), dim3(256), st, E, fd, g->dst, g->src, inv,
+           g->ecsc, xc, out);
+  else
+    launch(dec_kernel<int64_t>(g->f32, d.edge_out), dim3(tgrid(E)), dim3(256), st, E, fd, edge_index,
+           edge_index + E, inv, g->ecsc, xc, out);
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }

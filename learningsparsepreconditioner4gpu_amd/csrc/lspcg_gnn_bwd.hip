@@ -351,8 +351,8 @@ __global__ void __launch_bounds__(64) k_edge_layer(int64_t E, const float* __res
   const int lane = threadIdx.x, it = lane & 15, q = lane >> 4;
   if constexpr (BWD) clear_block(gacc, 2 * FFG, lane);
   [[maybe_unused]] int done = 0;
-  const float* gedge = wl + 2 * H + ff_size(H, H);
-  const float* gmsg = gedge + 6 * H + ff_size(3 * H, H);
+  const float* gedge = wl + gnn_layer_off(kFFEdge);
+  const float* gmsg = wl + gnn_layer_off(kFFMsg);
   load_ff<3>(we, gedge + 6 * H, 3 * H, H, gedge, lane);
   load_ff<3>(wm, gmsg + 6 * H, 3 * H, H, gmsg, lane);
   __syncthreads();
@@ -554,26 +554,11 @@ __global__ void __launch_bounds__(256) k_reduce(const double* __restrict__ part,
 __global__ void __launch_bounds__(256) k_unfold(int node_in, int edge_in, int nlayers, int edge_out,
                                                 const double* __restrict__ gsum, const float* __restrict__ wts,
                                                 float* __restrict__ gw) {
-  const int b = blockIdx.x;
-  const int64_t enc = ff_size(node_in, H) + ff_size(edge_in, H);
-  const int64_t lsz = (2 * H + ff_size(H, H)) + 2 * (6 * H + ff_size(3 * H, H));
-  int in = 3 * H, out = H;
-  bool ln = true;
-  int64_t off;
-  if (b == 0) {
-    in = node_in, ln = false, off = 0;
-  } else if (b == 1) {
-    in = edge_in, ln = false, off = ff_size(node_in, H);
-  } else if (b == 2 + 3 * nlayers) {
-    ln = false, out = edge_out, off = enc + lsz * nlayers;
-  } else {
-    const int l = (b - 2) / 3, r = (b - 2) % 3;
-    off = enc + lsz * l;
-    if (r == 0) in = H;
-    if (r >= 1) off += 2 * H + ff_size(H, H);
-    if (r == 2) off += 6 * H + ff_size(3 * H, H);
-  }
-  const double* G = gsum + int64_t(b) * FFG;
+  const FFBlock B = gnn_ff_block(node_in, edge_in, nlayers, edge_out, blockIdx.x);
+  const int in = B.in, out = B.out;
+  const bool ln = B.ln;
+  const int64_t off = B.off;
+  const double* G = gsum + int64_t(blockIdx.x) * FFG;
   const int lnsz = ln ? 2 * in : 0;
   const float* gam = wts + off;
   const float* W1 = wts + off + lnsz;
@@ -638,9 +623,9 @@ int grid_for(int64_t items) {
   const int64_t t = (items + 15) / 16;
   return int(t < 1 ? 1 : (t > kMaxGrid ? kMaxGrid : t));
 }
-int egrid(int64_t n) {
-  const int64_t g = (n + 255) / 256;
-  return int(g < 1 ? 1 : (g > 16384 ? 16384 : g));
+template <bool BWD, typename... A>
+void launch_enc(int fin, int grid, hipStream_t st, A... args) {  // one 16-wide input block, or two (fin <= 32)
+  launch(fin <= 16 ? k_enc<1, BWD> : k_enc<2, BWD>, dim3(grid), dim3(64), st, args...);
 }
 
 int bwd_reserve(lspcg_gnn* g, int64_t N, int64_t E) {
@@ -674,15 +659,15 @@ int bwd_bysrc(lspcg_gnn* g, int64_t N, int64_t E, const int64_t* edge_index) {
   if (w.sei == edge_index && w.sN == N && w.sE == E) return LSPCG_OK;
   hipStream_t st = g->ctx->stream;
   LSPCG_HIP(hipMemsetAsync(w.scnt, 0, sizeof(int32_t) * (N + 1), st));
-  hipLaunchKernelGGL(k_bysrc_count, dim3(egrid(E)), dim3(256), 0, st, E, g->src, w.scnt);
+  launch(k_bysrc_count, dim3(egrid(E)), dim3(256), st, E, g->src, w.scnt);
   size_t tb = 0;
   LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, w.scnt, w.sptr, int(N + 1), st));
   LSPCG_CHECK(tb <= g->scan_bytes || tb <= 1, LSPCG_ERR_HIP, "gnn_backward: scan workspace too small");
   tb = g->scan_bytes ? g->scan_bytes : 1;
   LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(g->scan_tmp, tb, w.scnt, w.sptr, int(N + 1), st));
   LSPCG_HIP(hipMemsetAsync(w.scnt, 0, sizeof(int32_t) * (N + 1), st));
-  hipLaunchKernelGGL(k_bysrc_fill, dim3(egrid(E)), dim3(256), 0, st, E, g->src, w.sptr, w.scnt, w.sslot);
-  hipLaunchKernelGGL(k_bysrc_sort, dim3(egrid(N)), dim3(256), 0, st, N, w.sptr, w.sslot);
+  launch(k_bysrc_fill, dim3(egrid(E)), dim3(256), st, E, g->src, w.sptr, w.scnt, w.sslot);
+  launch(k_bysrc_sort, dim3(egrid(N)), dim3(256), st, N, w.sptr, w.sslot);
   LSPCG_HIP(hipGetLastError());
   w.sei = edge_index;
   w.sN = N;
@@ -691,8 +676,8 @@ int bwd_bysrc(lspcg_gnn* g, int64_t N, int64_t E, const int64_t* edge_index) {
 }
 
 int reduce_into(lspcg_gnn* g, int P, int size, int ff_index) {
-  hipLaunchKernelGGL(k_reduce, dim3((size + 63) / 64), dim3(256), 0, g->ctx->stream, g->bw.part, P, size,
-                     g->bw.gsum + int64_t(ff_index) * FFG);
+  launch(k_reduce, dim3((size + 63) / 64), dim3(256), g->ctx->stream, g->bw.part, P, size,
+         g->bw.gsum + int64_t(ff_index) * FFG);
   return LSPCG_OK;
 }
 
@@ -737,87 +722,50 @@ extern "C" int lspcg_gnn_backward(lspcg_gnn* g, int64_t N, int64_t E, const floa
   const int gN = grid_for(N), gE = grid_for(E);
   const int64_t nN = N * H, nE = E * H;
   const float* wts = g->wdev;
-  const float* w_nenc = wts;
-  const float* w_eenc = wts + ff_size(d.node_in, H);
-  const int64_t enc = ff_size(d.node_in, H) + ff_size(d.edge_in, H);
-  const int64_t lsz = (2 * H + ff_size(H, H)) + 2 * (6 * H + ff_size(3 * H, H));
-  const float* w_dec = wts + enc + lsz * L;
-  float* const null_f = nullptr;
-  double* const null_p = nullptr;
-  const float* const null_c = nullptr;
-  const int32_t* const null_i = nullptr;
-  LSPCG_HIP(hipMemsetAsync(w.gsum, 0, sizeof(double) * FFG * size_t(3 + 3 * L), st));
+  auto blob_at = [&](int b) { return wts + gnn_ff_block(d, b).off; };  // FeedForward b of the packed weights
+  const float *w_nenc = blob_at(0), *w_eenc = blob_at(1), *w_dec = blob_at(gnn_ff_dec(L));
+  LSPCG_HIP(hipMemsetAsync(w.gsum, 0, sizeof(double) * FFG * size_t(gnn_ff_count(L)), st));
 
   // ---- training forward: x_0, e_0, then per layer msg -> a_l, x_{l+1}, e_{l+1}
-  if (d.node_in <= 16)
-    hipLaunchKernelGGL((k_enc<1, false>), dim3(gN), dim3(64), 0, st, N, w_nenc, d.node_in, x, null_i, w.xs, null_c,
-                       null_p);
-  else
-    hipLaunchKernelGGL((k_enc<2, false>), dim3(gN), dim3(64), 0, st, N, w_nenc, d.node_in, x, null_i, w.xs, null_c,
-                       null_p);
-  if (d.edge_in <= 16)
-    hipLaunchKernelGGL((k_enc<1, false>), dim3(gE), dim3(64), 0, st, E, w_eenc, d.edge_in, edge_attr,
-                       static_cast<const int32_t*>(g->perm), w.es, null_c, null_p);
-  else
-    hipLaunchKernelGGL((k_enc<2, false>), dim3(gE), dim3(64), 0, st, E, w_eenc, d.edge_in, edge_attr,
-                       static_cast<const int32_t*>(g->perm), w.es, null_c, null_p);
+  launch_enc<false>(d.node_in, gN, st, N, w_nenc, d.node_in, x, nullptr, w.xs, nullptr, nullptr);
+  launch_enc<false>(d.edge_in, gE, st, E, w_eenc, d.edge_in, edge_attr, g->perm, w.es, nullptr, nullptr);
   for (int l = 0; l < L; ++l) {
-    const float* wl = wts + enc + lsz * l;
-    hipLaunchKernelGGL(k_edge_layer<false>, dim3(gE), dim3(64), 0, st, E, wl, d.edge_residual,
-                       static_cast<const int32_t*>(g->src), static_cast<const int32_t*>(g->dst),
-                       static_cast<const float*>(w.xs + nN * l), static_cast<const float*>(w.es + nE * l),
-                       w.es + nE * (l + 1), w.dfd, null_c, null_f, null_f, null_f, null_p);
-    hipLaunchKernelGGL(k_node_layer<false>, dim3(gN), dim3(64), 0, st, N, wl, d.node_residual,
-                       static_cast<const int32_t*>(g->ptr), static_cast<const float*>(w.dfd),
-                       static_cast<const float*>(w.xs + nN * l), w.as + nN * l, w.xs + nN * (l + 1), null_c, null_f,
-                       null_p);
+    const float* wl = blob_at(gnn_ff_index(l, kFFNode));  // the layer's [node | edge | msg]
+    launch(k_edge_layer<false>, dim3(gE), dim3(64), st, E, wl, d.edge_residual, g->src, g->dst, w.xs + nN * l,
+           w.es + nE * l, w.es + nE * (l + 1), w.dfd, nullptr, nullptr, nullptr, nullptr, nullptr);
+    launch(k_node_layer<false>, dim3(gN), dim3(64), st, N, wl, d.node_residual, g->ptr, w.dfd, w.xs + nN * l,
+           w.as + nN * l, w.xs + nN * (l + 1), nullptr, nullptr, nullptr);
   }
 
   // ---- decoder
-  hipLaunchKernelGGL(k_dec_bwd, dim3(gE), dim3(64), 0, st, E, w_dec, d.edge_out, static_cast<const int32_t*>(g->src),
-                     static_cast<const int32_t*>(g->dst), static_cast<const int32_t*>(g->perm),
-                     static_cast<const float*>(w.xs + nN * L), static_cast<const float*>(w.es + nE * L), grad_out,
-                     w.de, w.dfd, w.dfs, w.part);
-  reduce_into(g, gE, FFG, 2 + 3 * L);
+  launch(k_dec_bwd, dim3(gE), dim3(64), st, E, w_dec, d.edge_out, g->src, g->dst, g->perm, w.xs + nN * L,
+         w.es + nE * L, grad_out, w.de, w.dfd, w.dfs, w.part);
+  reduce_into(g, gE, FFG, gnn_ff_dec(L));
   float* dx = w.dxa;
   float* dx2 = w.dxb;
   const unsigned gg = unsigned((N * 4 + 255) / 256);
-  hipLaunchKernelGGL(k_gather, dim3(gg), dim3(256), 0, st, N, static_cast<const int32_t*>(g->ptr), sptr, sslot, null_c,
-                     static_cast<const float*>(w.dfd), static_cast<const float*>(w.dfs), dx);
+  launch(k_gather, dim3(gg), dim3(256), st, N, g->ptr, sptr, sslot, nullptr, w.dfd, w.dfs, dx);
   // ---- layers in reverse
   for (int l = L - 1; l >= 0; --l) {
-    const float* wl = wts + enc + lsz * l;
-    hipLaunchKernelGGL(k_node_layer<true>, dim3(gN), dim3(64), 0, st, N, wl, d.node_residual,
-                       static_cast<const int32_t*>(g->ptr), null_c, null_c, w.as + nN * l, null_f,
-                       static_cast<const float*>(dx), w.da, w.part);
-    reduce_into(g, gN, FFG, 2 + 3 * l);
-    hipLaunchKernelGGL(k_edge_layer<true>, dim3(gE), dim3(64), 0, st, E, wl, d.edge_residual,
-                       static_cast<const int32_t*>(g->src), static_cast<const int32_t*>(g->dst),
-                       static_cast<const float*>(w.xs + nN * l), static_cast<const float*>(w.es + nE * l), null_f,
-                       null_f, static_cast<const float*>(w.da), w.de, w.dfd, w.dfs, w.part);
-    reduce_into(g, gE, 2 * FFG, 3 + 3 * l);  // [edge | msg]
-    hipLaunchKernelGGL(k_gather, dim3(gg), dim3(256), 0, st, N, static_cast<const int32_t*>(g->ptr), sptr, sslot,
-                       d.node_residual ? static_cast<const float*>(dx) : null_c, static_cast<const float*>(w.dfd),
-                       static_cast<const float*>(w.dfs), dx2);
+    const float* wl = blob_at(gnn_ff_index(l, kFFNode));
+    launch(k_node_layer<true>, dim3(gN), dim3(64), st, N, wl, d.node_residual, g->ptr, nullptr, nullptr,
+           w.as + nN * l, nullptr, dx, w.da, w.part);
+    reduce_into(g, gN, FFG, gnn_ff_index(l, kFFNode));
+    launch(k_edge_layer<true>, dim3(gE), dim3(64), st, E, wl, d.edge_residual, g->src, g->dst, w.xs + nN * l,
+           w.es + nE * l, nullptr, nullptr, w.da, w.de, w.dfd, w.dfs, w.part);
+    static_assert(kFFMsg == kFFEdge + 1, "k_edge_layer's partial block is [edge | msg], two neighbours of gsum");
+    reduce_into(g, gE, 2 * FFG, gnn_ff_index(l, kFFEdge));
+    launch(k_gather, dim3(gg), dim3(256), st, N, g->ptr, sptr, sslot, d.node_residual ? dx : nullptr, w.dfd, w.dfs,
+           dx2);
     std::swap(dx, dx2);
   }
   // ---- encoders
-  if (d.node_in <= 16)
-    hipLaunchKernelGGL((k_enc<1, true>), dim3(gN), dim3(64), 0, st, N, w_nenc, d.node_in, x, null_i, null_f,
-                       static_cast<const float*>(dx), w.part);
-  else
-    hipLaunchKernelGGL((k_enc<2, true>), dim3(gN), dim3(64), 0, st, N, w_nenc, d.node_in, x, null_i, null_f,
-                       static_cast<const float*>(dx), w.part);
+  launch_enc<true>(d.node_in, gN, st, N, w_nenc, d.node_in, x, nullptr, nullptr, dx, w.part);
   reduce_into(g, gN, FFG, 0);
-  if (d.edge_in <= 16)
-    hipLaunchKernelGGL((k_enc<1, true>), dim3(gE), dim3(64), 0, st, E, w_eenc, d.edge_in, edge_attr,
-                       static_cast<const int32_t*>(g->perm), null_f, static_cast<const float*>(w.de), w.part);
-  else
-    hipLaunchKernelGGL((k_enc<2, true>), dim3(gE), dim3(64), 0, st, E, w_eenc, d.edge_in, edge_attr,
-                       static_cast<const int32_t*>(g->perm), null_f, static_cast<const float*>(w.de), w.part);
+  launch_enc<true>(d.edge_in, gE, st, E, w_eenc, d.edge_in, edge_attr, g->perm, nullptr, w.de, w.part);
   reduce_into(g, gE, FFG, 1);
-  hipLaunchKernelGGL(k_unfold, dim3(3 + 3 * L), dim3(256), 0, st, d.node_in, d.edge_in, L, d.edge_out,
-                     static_cast<const double*>(w.gsum), wts, grad_weights);
+  launch(k_unfold, dim3(gnn_ff_count(L)), dim3(256), st, d.node_in, d.edge_in, L, d.edge_out, w.gsum, wts,
+         grad_weights);
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }

@@ -109,6 +109,17 @@ inline KernelTimer*& kernel_timer() {
     }                                                                                                    \
   } while (0)
 
+// hipLaunchKernelGGL (no dynamic LDS) with the argument types taken from the kernel's signature, so
+// the arguments convert implicitly (nullptr, T* -> const T*, int -> int64_t) instead of by a cast
+template <typename T>
+struct arg_of {
+  using type = T;
+};
+template <typename... P>
+inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st, typename arg_of<P>::type... args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+}
+
 constexpr int kThreads = 256;       // 4 wave64 per workgroup
 constexpr int kElemBlocksMax = 2048;  // grid cap for streaming elementwise kernels
 // grid_reduce_dd ticket buffer: [top | group 0 | group 1 | ...], one 128-B line each
