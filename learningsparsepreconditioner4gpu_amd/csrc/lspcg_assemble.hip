@@ -183,25 +183,22 @@ template <typename TO, typename TI, typename TM, int BS>
 static int assemble_t(lspcg_ctx* ctx, int64_t nb, int64_t E, const int64_t* ei, const void* blocks, const void* mask,
                       int out_dtype, int out_block, lspcg_mat** out) {
   hipStream_t st = ctx->stream;
+  DevBuf B;
   int32_t* bptr = nullptr;
   int* flag = nullptr;
-  LSPCG_HIP(hipMalloc(&bptr, sizeof(int32_t) * (nb + 1)));
-  LSPCG_HIP(hipMalloc(&flag, sizeof(int)));
-  std::unique_ptr<void, void (*)(void*)> g1(bptr, [](void* p) { (void)hipFree(p); });
-  std::unique_ptr<void, void (*)(void*)> g2(flag, [](void* p) { (void)hipFree(p); });
+  if (int rc = B.get(&bptr, nb + 1) | B.get(&flag, 1)) return rc;
   LSPCG_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
   if (E > 0) hipLaunchKernelGGL(k_check_edges, dim3(grid_of(E)), dim3(kThreads), 0, st, E, nb, ei, flag);
   hipLaunchKernelGGL(k_block_rowptr, dim3(grid_of(nb + 1)), dim3(kThreads), 0, st, E, nb, ei, bptr);
   int hflag = 0;
-  LSPCG_HIP(hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  LSPCG_HIP(hipStreamSynchronize(st));
+  if (int rc = flag_value(flag, st, &hflag)) return rc;
   LSPCG_CHECK(!(hflag & 1), LSPCG_ERR_FORMAT, "assemble: edge_index out of range");
   LSPCG_CHECK(!(hflag & 2), LSPCG_ERR_FORMAT,
               "assemble: edge_index must be row-major sorted without duplicates (make_bsr_from_coo_inds contract)");
   AsmIn<TO, TI, TM> in{nb, E, ei, static_cast<const TI*>(blocks), static_cast<const TM*>(mask), bptr};
   const int64_t n = nb * BS;
 
-  std::unique_ptr<lspcg_mat> m(new lspcg_mat());
+  std::unique_ptr<lspcg_mat, int (*)(lspcg_mat*)> m(new lspcg_mat(), lspcg_mat_destroy);
   m->ctx = ctx;
   m->dtype = out_dtype;
   if (out_block) {
@@ -213,13 +210,9 @@ static int assemble_t(lspcg_ctx* ctx, int64_t nb, int64_t E, const int64_t* ei, 
     if (int rc = mat_alloc_entries(m.get(), E)) return rc;
     hipLaunchKernelGGL((k_asm_bsr<TO, TI, TM, BS>), dim3(grid_of(nb)), dim3(kThreads), 0, st, in, m->rowptr,
                        m->colind, static_cast<TO*>(m->vals), flag);
-    LSPCG_HIP(hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    LSPCG_HIP(hipStreamSynchronize(st));
-    if (hflag & 4) {
-      lspcg_mat_destroy(m.release());
-      set_error("assemble: BSR output needs the diagonal block of every Dirichlet-masked block row");
-      return LSPCG_ERR_FORMAT;
-    }
+    if (int rc = flag_value(flag, st, &hflag)) return rc;
+    LSPCG_CHECK(!(hflag & 4), LSPCG_ERR_FORMAT,
+                "assemble: BSR output needs the diagonal block of every Dirichlet-masked block row");
     *out = m.release();
     return LSPCG_OK;
   }
@@ -229,20 +222,19 @@ static int assemble_t(lspcg_ctx* ctx, int64_t nb, int64_t E, const int64_t* ei, 
   m->n = n;
   LSPCG_HIP(hipMalloc(&m->rowptr, sizeof(int32_t) * (n + 1)));
   int32_t* cnt = nullptr;  // counts in [0,n) (+ a zero at n), scanned into rowptr[0..n]
-  LSPCG_HIP(hipMalloc(&cnt, sizeof(int32_t) * (n + 1)));
-  std::unique_ptr<void, void (*)(void*)> g3(cnt, [](void* p) { (void)hipFree(p); });
+  if (int rc = B.get(&cnt, n + 1)) return rc;
   hipLaunchKernelGGL((k_asm_rows<TO, TI, TM, BS, false>), dim3(seg_grid(n)), dim3(256), 0, st, in,
                      static_cast<const int32_t*>(nullptr), cnt, static_cast<int32_t*>(nullptr), static_cast<TO*>(nullptr));
   LSPCG_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int32_t), st));
   size_t tmp_bytes = 0;
   LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt, m->rowptr, int(n + 1), st));
+  DevBuf scan;
   void* tmp = nullptr;
-  LSPCG_HIP(hipMalloc(&tmp, tmp_bytes > 0 ? tmp_bytes : 1));
+  if (int rc = scan.get(&tmp, tmp_bytes)) return rc;
   LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, m->rowptr, int(n + 1), st));
   int32_t nnz = 0;
-  LSPCG_HIP(hipMemcpyAsync(&nnz, m->rowptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  LSPCG_HIP(hipStreamSynchronize(st));
-  (void)hipFree(tmp);
+  if (int rc = flag_value(m->rowptr + n, st, &nnz)) return rc;
+  scan.release();
   m->nnzb = nnz;
   if (int rc = mat_alloc_entries(m.get(), nnz)) return rc;
   hipLaunchKernelGGL((k_asm_rows<TO, TI, TM, BS, true>), dim3(seg_grid(n)), dim3(256), 0, st, in, m->rowptr,

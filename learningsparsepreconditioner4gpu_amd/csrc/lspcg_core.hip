@@ -184,16 +184,6 @@ static int grid_for(int64_t n) {
   return int(std::max<int64_t>(1, std::min<int64_t>(g, kElemBlocksMax)));
 }
 
-template <typename T, int BS>
-inline void launch_transpose_fill(const lspcg_mat* A, lspcg_mat* Tm, int32_t* fill, int32_t* trow, int64_t* tsrc,
-                                  hipStream_t st) {
-  const int g = grid_for(A->nb);
-  hipLaunchKernelGGL(k_scatter_transpose, dim3(g), dim3(kThreads), 0, st, A->nb, A->rowptr, A->colind, Tm->rowptr,
-                     fill, trow, tsrc);
-  hipLaunchKernelGGL((k_sort_gather_transpose<T, BS>), dim3(g), dim3(kThreads), 0, st, A->nb, Tm->rowptr, trow, tsrc,
-                     static_cast<const T*>(A->vals), static_cast<T*>(Tm->vals));
-}
-
 // diagnostic gather: one 16-B load of an interleaved pair, a - alpha*b (the fused schedule's
 // r - alpha q / p beta + z gathers with the two vectors interleaved)
 struct GatherPairDiag {
@@ -296,6 +286,30 @@ int mat_alloc(lspcg_ctx* ctx, int64_t nb, int64_t nnzb, int bs, int dtype, lspcg
   *out = m.release();
   return LSPCG_OK;
 }
+
+int scan_to_rowptr(const int32_t* cnt, int64_t n, int32_t* rowptr, int64_t* total, hipStream_t st) {
+  std::vector<int32_t> h(n + 1);
+  if (n) LSPCG_HIP(hipMemcpyAsync(h.data(), cnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  LSPCG_HIP(hipStreamSynchronize(st));
+  int64_t acc = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t c = h[i];
+    h[i] = int32_t(acc);
+    acc += c;
+  }
+  LSPCG_CHECK(acc < (int64_t(1) << 31), LSPCG_ERR_ARG, "pattern too large for int32 indices");
+  h[n] = int32_t(acc);
+  LSPCG_HIP(hipMemcpyAsync(rowptr, h.data(), sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, st));
+  LSPCG_HIP(hipStreamSynchronize(st));
+  *total = acc;
+  return LSPCG_OK;
+}
+
+int flag_value(const int* dflag, hipStream_t st, int* out) {
+  LSPCG_HIP(hipMemcpyAsync(out, dflag, sizeof(int), hipMemcpyDeviceToHost, st));
+  LSPCG_HIP(hipStreamSynchronize(st));
+  return LSPCG_OK;
+}
 }  // namespace lspcg
 
 extern "C" {
@@ -387,99 +401,54 @@ int lspcg::mat_transpose(const lspcg_mat* A, lspcg_mat** out, bool* same_pattern
   lspcg_mat* Tm = nullptr;
   // a previous transpose of a matrix of the same shape is overwritten in place (a new ext_spai factor
   // on the same solver: no free / allocate of the entry arrays, and its addresses stay valid)
-  if (A->storage_dtype() == A->dtype && mat_reusable(reuse, A)) {
-    Tm = reuse;
-  } else {
-    reuse = nullptr;
-    int rc = mat_alloc(ctx, A->nb, A->nnzb, A->block_size, A->dtype, &Tm);
-    if (rc) return rc;
+  if (A->storage_dtype() == A->dtype && mat_reusable(reuse, A)) Tm = reuse;
+  else if (int rc = mat_alloc(ctx, A->nb, A->nnzb, A->block_size, A->dtype, &Tm)) return rc;
+  // an early return destroys Tm unless it is the caller's `reuse`; handed out through release()
+  std::unique_ptr<lspcg_mat, int (*)(lspcg_mat*)> guard(Tm == reuse ? nullptr : Tm, lspcg_mat_destroy);
+  DevBuf B;
+  // symmetric pattern (the ext_spai factor always has A's pattern): value permutation only
+  int* flag = nullptr;
+  if (int rc = B.get(&flag, 1)) return rc;
+  LSPCG_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+  LSPCG_HIP(hipMemcpyAsync(Tm->rowptr, A->rowptr, sizeof(int32_t) * (A->nb + 1), hipMemcpyDeviceToDevice, st));
+  if (A->nnzb) LSPCG_HIP(hipMemcpyAsync(Tm->colind, A->colind, sizeof(int32_t) * A->nnzb, hipMemcpyDeviceToDevice, st));
+  if (A->nb) {
+    const dim3 g(unsigned(std::min<int64_t>((A->nb + kTrRows - 1) / kTrRows, 65535))), b(kTrRows);
+    by_dtype_bs(A->dtype, A->block_size, [&](auto t, auto bs) {
+      using T = decltype(t);
+      launch(k_transpose_sym<T, decltype(bs)::value>, g, b, st, A->nb, A->rowptr, A->colind, as<T>(A->vals),
+             as<T>(Tm->vals), flag);
+    });
+    LSPCG_HIP(hipGetLastError());
   }
-  auto drop = [&]() {
-    if (Tm != reuse) lspcg_mat_destroy(Tm);
-  };
-  {  // symmetric pattern (the ext_spai factor always has A's pattern): value permutation only
-    int* flag = nullptr;
-    int h = 1;
-    hipError_t e = hipMalloc(&flag, sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), st);
-    if (e == hipSuccess) e = hipMemcpyAsync(Tm->rowptr, A->rowptr, sizeof(int32_t) * (A->nb + 1), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && A->nnzb)
-      e = hipMemcpyAsync(Tm->colind, A->colind, sizeof(int32_t) * A->nnzb, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && A->nb) {
-      const dim3 g(unsigned(std::min<int64_t>((A->nb + kTrRows - 1) / kTrRows, 65535))), b(kTrRows);
-      if (A->dtype == LSPCG_F64) {
-        if (A->block_size == 1)
-          hipLaunchKernelGGL((k_transpose_sym<double, 1>), g, b, 0, st, A->nb, A->rowptr, A->colind,
-                             static_cast<const double*>(A->vals), static_cast<double*>(Tm->vals), flag);
-        else
-          hipLaunchKernelGGL((k_transpose_sym<double, 3>), g, b, 0, st, A->nb, A->rowptr, A->colind,
-                             static_cast<const double*>(A->vals), static_cast<double*>(Tm->vals), flag);
-      } else {
-        if (A->block_size == 1)
-          hipLaunchKernelGGL((k_transpose_sym<float, 1>), g, b, 0, st, A->nb, A->rowptr, A->colind,
-                             static_cast<const float*>(A->vals), static_cast<float*>(Tm->vals), flag);
-        else
-          hipLaunchKernelGGL((k_transpose_sym<float, 3>), g, b, 0, st, A->nb, A->rowptr, A->colind,
-                             static_cast<const float*>(A->vals), static_cast<float*>(Tm->vals), flag);
-      }
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(flag);
-    if (e != hipSuccess) {
-      set_error(std::string("transpose: ") + hipGetErrorString(e));
-      drop();
-      return LSPCG_ERR_HIP;
-    }
-    if (h == 0) {
-      if (same_pattern) *same_pattern = true;
-      *out = Tm;
-      return LSPCG_OK;
-    }
+  int missing = 1;
+  if (int rc = flag_value(flag, st, &missing)) return rc;
+  B.release();
+  if (!missing) {
+    if (same_pattern) *same_pattern = true;
+    guard.release();
+    *out = Tm;
+    return LSPCG_OK;
   }
+  // general pattern: counts -> host exclusive scan (setup path, not the solve loop) -> fill
   int32_t* cnt = nullptr;
   int64_t* tsrc = nullptr;
-  auto fail = [&](hipError_t e) {
-    set_error(std::string("transpose: ") + hipGetErrorString(e));
-    (void)hipFree(cnt);
-    (void)hipFree(tsrc);
-    drop();
-    return LSPCG_ERR_HIP;
-  };
-  hipError_t e = hipMalloc(&cnt, sizeof(int32_t) * (A->nb + 1));
-  if (e == hipSuccess) e = hipMalloc(&tsrc, sizeof(int64_t) * std::max<int64_t>(A->nnzb, 1));
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (A->nb + 1), st);
-  if (e != hipSuccess) return fail(e);
-  // counts -> host exclusive scan (nb+1 ints; setup path, not the solve loop)
-  hipLaunchKernelGGL(k_count_cols, dim3(grid_for(A->nnzb)), dim3(kThreads), 0, st, A->nnzb, A->colind, cnt);
-  std::vector<int32_t> h(A->nb + 1);
-  e = hipMemcpyAsync(h.data(), cnt, sizeof(int32_t) * A->nb, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(e);
-  int64_t acc = 0;
-  for (int64_t i = 0; i < A->nb; ++i) {
-    const int32_t c = h[i];
-    h[i] = int32_t(acc);
-    acc += c;
-  }
-  h[A->nb] = int32_t(acc);
-  e = hipMemcpyAsync(Tm->rowptr, h.data(), sizeof(int32_t) * (A->nb + 1), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (A->nb + 1), st);
-  if (e != hipSuccess) return fail(e);
-  if (A->dtype == LSPCG_F64) {
-    if (A->block_size == 1) launch_transpose_fill<double, 1>(A, Tm, cnt, Tm->colind, tsrc, st);
-    else launch_transpose_fill<double, 3>(A, Tm, cnt, Tm->colind, tsrc, st);
-  } else {
-    if (A->block_size == 1) launch_transpose_fill<float, 1>(A, Tm, cnt, Tm->colind, tsrc, st);
-    else launch_transpose_fill<float, 3>(A, Tm, cnt, Tm->colind, tsrc, st);
-  }
-  e = hipStreamSynchronize(st);
-  (void)hipFree(cnt);
-  (void)hipFree(tsrc);
-  cnt = nullptr;
-  tsrc = nullptr;
-  if (e != hipSuccess) return fail(e);
+  int64_t total = 0;
+  if (int rc = B.get(&cnt, A->nb + 1) | B.get(&tsrc, A->nnzb)) return rc;
+  LSPCG_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (A->nb + 1), st));
+  launch(k_count_cols, dim3(grid_for(A->nnzb)), dim3(kThreads), st, A->nnzb, A->colind, cnt);
+  if (int rc = scan_to_rowptr(cnt, A->nb, Tm->rowptr, &total, st)) return rc;
+  LSPCG_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (A->nb + 1), st));
+  const dim3 g(grid_for(A->nb)), b(kThreads);
+  launch(k_scatter_transpose, g, b, st, A->nb, A->rowptr, A->colind, Tm->rowptr, cnt, Tm->colind, tsrc);
+  by_dtype_bs(A->dtype, A->block_size, [&](auto t, auto bs) {
+    using T = decltype(t);
+    launch(k_sort_gather_transpose<T, decltype(bs)::value>, g, b, st, A->nb, Tm->rowptr, Tm->colind, tsrc,
+           as<T>(A->vals), as<T>(Tm->vals));
+  });
+  LSPCG_HIP(hipGetLastError());
+  LSPCG_HIP(hipStreamSynchronize(st));
+  guard.release();
   *out = Tm;
   return LSPCG_OK;
 }
@@ -489,22 +458,11 @@ extern "C" {
 int lspcg_mat_diagonal(const lspcg_mat* A, void* d) {
   LSPCG_CHECK(A && d, LSPCG_ERR_ARG, "diagonal: NULL");
   hipStream_t st = A->ctx->stream;
-  const int g = grid_for(A->nb);
-  if (A->dtype == LSPCG_F64) {
-    if (A->block_size == 1)
-      hipLaunchKernelGGL((k_diagonal<double, 1>), dim3(g), dim3(kThreads), 0, st, A->nb, A->rowptr, A->colind,
-                         static_cast<const double*>(A->vals), static_cast<double*>(d));
-    else
-      hipLaunchKernelGGL((k_diagonal<double, 3>), dim3(g), dim3(kThreads), 0, st, A->nb, A->rowptr, A->colind,
-                         static_cast<const double*>(A->vals), static_cast<double*>(d));
-  } else {
-    if (A->block_size == 1)
-      hipLaunchKernelGGL((k_diagonal<float, 1>), dim3(g), dim3(kThreads), 0, st, A->nb, A->rowptr, A->colind,
-                         static_cast<const float*>(A->vals), static_cast<float*>(d));
-    else
-      hipLaunchKernelGGL((k_diagonal<float, 3>), dim3(g), dim3(kThreads), 0, st, A->nb, A->rowptr, A->colind,
-                         static_cast<const float*>(A->vals), static_cast<float*>(d));
-  }
+  by_dtype_bs(A->dtype, A->block_size, [&](auto t, auto bs) {
+    using T = decltype(t);
+    launch(k_diagonal<T, decltype(bs)::value>, dim3(grid_for(A->nb)), dim3(kThreads), st, A->nb, A->rowptr, A->colind,
+           as<T>(A->vals), as<T>(d));
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -568,21 +526,11 @@ int lspcg_mat_scale_columns(lspcg_mat* A, const void* d) {
   drop_sell(A);  // values change: the SELL copy would be stale
   hipStream_t st = A->ctx->stream;
   const int g = grid_for(A->nnzb * A->block_size * A->block_size);
-  if (A->dtype == LSPCG_F64) {
-    if (A->block_size == 1)
-      hipLaunchKernelGGL((k_scale_columns<double, 1>), dim3(g), dim3(kThreads), 0, st, A->nnzb, A->colind,
-                         static_cast<double*>(A->vals), static_cast<const double*>(d));
-    else
-      hipLaunchKernelGGL((k_scale_columns<double, 3>), dim3(g), dim3(kThreads), 0, st, A->nnzb, A->colind,
-                         static_cast<double*>(A->vals), static_cast<const double*>(d));
-  } else {
-    if (A->block_size == 1)
-      hipLaunchKernelGGL((k_scale_columns<float, 1>), dim3(g), dim3(kThreads), 0, st, A->nnzb, A->colind,
-                         static_cast<float*>(A->vals), static_cast<const float*>(d));
-    else
-      hipLaunchKernelGGL((k_scale_columns<float, 3>), dim3(g), dim3(kThreads), 0, st, A->nnzb, A->colind,
-                         static_cast<float*>(A->vals), static_cast<const float*>(d));
-  }
+  by_dtype_bs(A->dtype, A->block_size, [&](auto t, auto bs) {
+    using T = decltype(t);
+    launch(k_scale_columns<T, decltype(bs)::value>, dim3(g), dim3(kThreads), st, A->nnzb, A->colind, as<T>(A->vals),
+           as<T>(d));
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -598,44 +546,26 @@ int lspcg_spmv(lspcg_ctx* ctx, const lspcg_mat* A, const void* x, void* y) {
     const int64_t nb = A->nb;
     const int32_t* pm = c->ro.perm;
     int rc = vec_permute(A->dtype, nb, A->block_size, pm, x, c->xs, false, ctx->stream);
-    if (!rc) {
-      hipStream_t st = ctx->stream;
-      if (A->dtype == LSPCG_F64) {
-        const GatherVec<double> gx{static_cast<const double*>(c->xs)};
-        if (A->block_size == 3)
-          launch_spmv_sell_cfg<double, double>(c->P, c->vals, gx, ProNone{}, EpiStorePerm<double, 3>{static_cast<double*>(y), pm}, st);
-        else
-          launch_spmv_sell_cfg<double, double>(c->P, c->vals, gx, ProNone{}, EpiStorePerm<double, 1>{static_cast<double*>(y), pm}, st);
-      } else {
-        const GatherVec<float> gx{static_cast<const float*>(c->xs)};
-        if (A->block_size == 3)
-          launch_spmv_sell_cfg<float, float>(c->P, c->vals, gx, ProNone{}, EpiStorePerm<float, 3>{static_cast<float*>(y), pm}, st);
-        else
-          launch_spmv_sell_cfg<float, float>(c->P, c->vals, gx, ProNone{}, EpiStorePerm<float, 1>{static_cast<float*>(y), pm}, st);
-      }
-    }
+    if (!rc)
+      by_dtype_bs(A->dtype, A->block_size, [&](auto t, auto bs) {
+        using T = decltype(t);
+        launch_spmv_sell_cfg<T, T>(c->P, c->vals, GatherVec<T>{as<T>(c->xs)}, ProNone{},
+                                   EpiStorePerm<T, decltype(bs)::value>{as<T>(y), pm}, ctx->stream);
+      });
     kernel_timer() = kt;
     if (rc) return rc;
     LSPCG_HIP(hipGetLastError());
     return LSPCG_OK;
   }
-  if (const SellCopy* c = A->sell) {
-    if (A->dtype == LSPCG_F64)
-      launch_spmv_sell_cfg<double, double>(c->P, c->vals, GatherVec<double>{static_cast<const double*>(x)}, ProNone{},
-                                           EpiStore<double>{static_cast<double*>(y)}, ctx->stream);
-    else
-      launch_spmv_sell_cfg<float, float>(c->P, c->vals, GatherVec<float>{static_cast<const float*>(x)}, ProNone{},
-                                         EpiStore<float>{static_cast<float*>(y)}, ctx->stream);
-    LSPCG_HIP(hipGetLastError());
-    return LSPCG_OK;
-  }
-  int rc;
-  if (A->dtype == LSPCG_F64)
-    rc = launch_spmv_any<double>(A, static_cast<const double*>(x), ProNone{}, EpiStore<double>{static_cast<double*>(y)},
-                                 ctx->stream);
-  else
-    rc = launch_spmv_any<float>(A, static_cast<const float*>(x), ProNone{}, EpiStore<float>{static_cast<float*>(y)},
-                                ctx->stream);
+  const int rc = by_dtype(A->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    const EpiStore<T> epi{as<T>(y)};
+    if (const SellCopy* c = A->sell) {
+      launch_spmv_sell_cfg<T, T>(c->P, c->vals, GatherVec<T>{as<T>(x)}, ProNone{}, epi, ctx->stream);
+      return LSPCG_OK;
+    }
+    return launch_spmv_any<T>(A, as<T>(x), ProNone{}, epi, ctx->stream);
+  });
   if (rc) return rc;
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
@@ -645,16 +575,31 @@ int lspcg_spmv(lspcg_ctx* ctx, const lspcg_mat* A, const void* x, void* y) {
 
 __global__ void k_noop() {}
 
+// the two timing events of a measurement, destroyed on every return
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int create() {
+    LSPCG_HIP(hipEventCreate(&e0));
+    LSPCG_HIP(hipEventCreate(&e1));
+    return LSPCG_OK;
+  }
+  ~EventPair() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
 template <class Launch>
 static int spmv_timed_impl(lspcg_ctx* ctx, const lspcg_mat* A, int reps, int64_t flush_bytes, double* avg_ms,
                            Launch launch) {
   LSPCG_CHECK(ctx && reps > 0 && avg_ms && flush_bytes >= 0, LSPCG_ERR_ARG, "spmv_timed: bad argument");
-  hipEvent_t e0, e1;
-  LSPCG_HIP(hipEventCreate(&e0));
-  LSPCG_HIP(hipEventCreate(&e1));
-  void* flush = nullptr;
+  EventPair ev;
+  if (int rc = ev.create()) return rc;
+  const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+  DevBuf B;
+  char* flush = nullptr;
   if (flush_bytes > 0) {
-    LSPCG_HIP(hipMalloc(&flush, size_t(flush_bytes) + 64));
+    if (int rc = B.get(&flush, size_t(flush_bytes) + 64)) return rc;
     LSPCG_HIP(hipMemsetAsync(flush, 1, size_t(flush_bytes) + 64, ctx->stream));
   }
   double total = 0.0;
@@ -676,8 +621,9 @@ static int spmv_timed_impl(lspcg_ctx* ctx, const lspcg_mat* A, int reps, int64_t
     // R x (flush + launch) - R x (flush + an empty one-workgroup kernel), which has the same number
     // of boundaries on both sides.
     auto flush_k = [&]() {
-      hipLaunchKernelGGL(k_flush_read, dim3(4096), dim3(kThreads), 0, ctx->stream, static_cast<const u32x4*>(flush),
-                         flush_bytes / 16, reinterpret_cast<unsigned*>(static_cast<char*>(flush) + flush_bytes));
+      hipLaunchKernelGGL(k_flush_read, dim3(4096), dim3(kThreads), 0, ctx->stream,
+                         reinterpret_cast<const u32x4*>(flush), flush_bytes / 16,
+                         reinterpret_cast<unsigned*>(flush + flush_bytes));
     };
     flush_k();
     if (int rc = launch()) return rc;  // untimed first pair
@@ -719,10 +665,7 @@ static int spmv_timed_impl(lspcg_ctx* ctx, const lspcg_mat* A, int reps, int64_t
     }
     LSPCG_HIP(hipGetLastError());
     total = stamped ? sum : double(t_pair) - double(t_flush);
-    (void)hipFree(flush);
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   *avg_ms = total / reps;
   return LSPCG_OK;
 }
@@ -757,15 +700,14 @@ int lspcg_spmv_sell_timed(lspcg_ctx* ctx, const lspcg_mat* A, int compact, const
                    ((compact & 16) ? kSellColJag : 0) | ((compact & 32) && !(compact & 4) ? kSellColXs : 0);
   int rc = sell_build_pattern(A->n, A->nnzb, A->rowptr, A->colind, 1e30, cols, st, &P);
   if (rc) return rc;
+  DevBuf B;
   void* v = nullptr;
   rc = sell_fill_values(P, A->colind, A->vals, LSPCG_F64, (compact & 1) ? LSPCG_F32 : LSPCG_F64, st, &v);
+  B.p.push_back(v);  // the filled values are this function's from here
   double* x2 = nullptr;
-  if (!rc && (compact & 4)) {  // experiment: 16-B gathers of interleaved (x, x) pairs
-    if (hipMalloc(&x2, sizeof(double) * 2 * std::max<int64_t>(A->n, 1)) != hipSuccess) rc = LSPCG_ERR_HIP;
-    else {
-      (void)hipMemcpy2DAsync(x2, 16, x, 8, 8, A->n, hipMemcpyDeviceToDevice, st);
-      (void)hipMemcpy2DAsync(x2 + 1, 16, x, 8, 8, A->n, hipMemcpyDeviceToDevice, st);
-    }
+  if (!rc && (compact & 4) && !(rc = B.get(&x2, 2 * A->n))) {  // experiment: 16-B gathers of interleaved (x, x) pairs
+    (void)hipMemcpy2DAsync(x2, 16, x, 8, 8, A->n, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpy2DAsync(x2 + 1, 16, x, 8, 8, A->n, hipMemcpyDeviceToDevice, st);
   }
   if (!rc) {
     const GatherVec<double> gx{static_cast<const double*>(x)};
@@ -784,28 +726,26 @@ int lspcg_spmv_sell_timed(lspcg_ctx* ctx, const lspcg_mat* A, int compact, const
     });
   }
   (void)hipStreamSynchronize(st);
-  (void)hipFree(x2);
-  (void)hipFree(v);
+  B.release();
   P.release();
   return rc;
 }
 
 int lspcg_read_timed(lspcg_ctx* ctx, int64_t bytes, int reps, int64_t flush_bytes, double* avg_ms) {
   LSPCG_CHECK(ctx && bytes >= 16 && reps > 0 && avg_ms, LSPCG_ERR_ARG, "read_timed: bad argument");
-  void* buf = nullptr;
-  LSPCG_HIP(hipMalloc(&buf, size_t(bytes) + 64));
+  DevBuf B;
+  char* buf = nullptr;
+  if (int rc = B.get(&buf, size_t(bytes) + 64)) return rc;
   LSPCG_HIP(hipMemsetAsync(buf, 2, size_t(bytes) + 64, ctx->stream));
   int g = 0;
   LSPCG_HIP(hipDeviceGetAttribute(&g, hipDeviceAttributeMultiprocessorCount, ctx->device));
   const int rc = spmv_timed_impl(ctx, nullptr, reps, flush_bytes, avg_ms, [&]() -> int {
     hipLaunchKernelGGL(k_flush_read, dim3(unsigned(g * 8)), dim3(kThreads), 0, ctx->stream,
-                       static_cast<const u32x4*>(buf), bytes / 16,
-                       reinterpret_cast<unsigned*>(static_cast<char*>(buf) + bytes));
+                       reinterpret_cast<const u32x4*>(buf), bytes / 16, reinterpret_cast<unsigned*>(buf + bytes));
     LSPCG_HIP(hipGetLastError());
     return LSPCG_OK;
   });
   (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(buf);
   return rc;
 }
 
@@ -813,22 +753,18 @@ int lspcg_dot(lspcg_ctx* ctx, int64_t n, int dtype, const void* x, const void* y
   LSPCG_CHECK(ctx && out && n >= 0 && (n == 0 || (x && y)), LSPCG_ERR_ARG, "dot: bad argument");
   hipStream_t st = ctx->stream;
   const int g = grid_for(n);
+  DevBuf B;
   double* buf = nullptr;  // [partials(2*g) | result]
   unsigned* ticket = nullptr;
-  LSPCG_HIP(hipMalloc(&buf, sizeof(double) * (2 * g + 1)));
-  LSPCG_HIP(hipMalloc(&ticket, sizeof(unsigned) * kTicketWords));
+  if (int rc = B.get(&buf, 2 * g + 1) | B.get(&ticket, kTicketWords)) return rc;
   LSPCG_HIP(hipMemsetAsync(ticket, 0, sizeof(unsigned) * kTicketWords, st));
-  if (dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_dot<double>, dim3(g), dim3(kThreads), 0, st, n, static_cast<const double*>(x),
-                       static_cast<const double*>(y), buf, ticket, buf + 2 * g);
-  else
-    hipLaunchKernelGGL(k_dot<float>, dim3(g), dim3(kThreads), 0, st, n, static_cast<const float*>(x),
-                       static_cast<const float*>(y), buf, ticket, buf + 2 * g);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_dot<T>, dim3(g), dim3(kThreads), st, n, as<T>(x), as<T>(y), buf, ticket, buf + 2 * g);
+  });
   LSPCG_HIP(hipGetLastError());
   LSPCG_HIP(hipMemcpyAsync(out, buf + 2 * g, sizeof(double), hipMemcpyDeviceToHost, st));
   LSPCG_HIP(hipStreamSynchronize(st));
-  (void)hipFree(buf);
-  (void)hipFree(ticket);
   return LSPCG_OK;
 }
 

@@ -69,78 +69,39 @@ __global__ void k_tril_fill(int64_t n, const int32_t* __restrict__ rp, const int
   }
 }
 
-// host exclusive scan of cnt[0..n) into a device rowptr (setup path, like lspcg_mat_transpose)
-static int scan_to_rowptr(const int32_t* cnt, int64_t n, int32_t* rowptr, int64_t* total, hipStream_t st) {
-  std::vector<int32_t> h(n + 1);
-  if (n) LSPCG_HIP(hipMemcpyAsync(h.data(), cnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-  LSPCG_HIP(hipStreamSynchronize(st));
-  int64_t acc = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t c = h[i];
-    h[i] = int32_t(acc);
-    acc += c;
-  }
-  LSPCG_CHECK(acc < (int64_t(1) << 31), LSPCG_ERR_ARG, "pattern too large for int32 indices");
-  h[n] = int32_t(acc);
-  LSPCG_HIP(hipMemcpyAsync(rowptr, h.data(), sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, st));
-  LSPCG_HIP(hipStreamSynchronize(st));
-  *total = acc;
-  return LSPCG_OK;
-}
-
-static int flag_value(int* dflag, hipStream_t st, int* out) {
-  LSPCG_HIP(hipMemcpyAsync(out, dflag, sizeof(int), hipMemcpyDeviceToHost, st));
-  LSPCG_HIP(hipStreamSynchronize(st));
-  return LSPCG_OK;
-}
+// an owned matrix under construction: destroyed on scope exit unless handed out
+using MatGuard = std::unique_ptr<lspcg_mat, int (*)(lspcg_mat*)>;
 
 // L <- tril(A) (values copied when with_vals)
 static int tril_of(const lspcg_mat* A, bool with_vals, lspcg_mat** out) {
   LSPCG_CHECK(A->block_size == 1, LSPCG_ERR_UNSUPPORTED, "tril: scalar CSR required (expand BSR first)");
   hipStream_t st = A->ctx->stream;
   const int64_t n = A->n;
-  int32_t* cnt = nullptr;
+  DevBuf B;
+  int32_t *cnt = nullptr, *tmp_rp = nullptr;
   int* flag = nullptr;
-  LSPCG_HIP(hipMalloc(&cnt, sizeof(int32_t) * std::max<int64_t>(n, 1)));
-  LSPCG_HIP(hipMalloc(&flag, sizeof(int)));
+  if (int rc = B.get(&cnt, n) | B.get(&flag, 1)) return rc;
   LSPCG_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_tril_count, dim3(fgrid(n)), dim3(kThreads), 0, st, n, A->rowptr, A->colind, cnt, flag);
+  launch(k_tril_count, dim3(fgrid(n)), dim3(kThreads), st, n, A->rowptr, A->colind, cnt, flag);
   int f = 0;
-  int rc = flag_value(flag, st, &f);
-  if (!rc && f) {
-    set_error("factor: a row of A has no stored diagonal entry");
-    rc = LSPCG_ERR_FORMAT;
-  }
-  lspcg_mat* L = nullptr;
+  if (int rc = flag_value(flag, st, &f)) return rc;
+  LSPCG_CHECK(!f, LSPCG_ERR_FORMAT, "factor: a row of A has no stored diagonal entry");
+  // count first, then allocate with the exact entry count
   int64_t total = 0;
-  if (!rc) {
-    // count first, then allocate with the exact entry count
-    int32_t* tmp_rp = nullptr;
-    LSPCG_HIP(hipMalloc(&tmp_rp, sizeof(int32_t) * (n + 1)));
-    rc = scan_to_rowptr(cnt, n, tmp_rp, &total, st);
-    if (!rc) rc = mat_alloc(A->ctx, n, total, 1, A->dtype, &L);
-    if (!rc) {
-      LSPCG_HIP(hipMemcpyAsync(L->rowptr, tmp_rp, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToDevice, st));
-      if (A->dtype == LSPCG_F64)
-        hipLaunchKernelGGL(k_tril_fill<double>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, A->rowptr, A->colind,
-                           static_cast<const double*>(A->vals), L->rowptr, L->colind,
-                           with_vals ? static_cast<double*>(L->vals) : nullptr);
-      else
-        hipLaunchKernelGGL(k_tril_fill<float>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, A->rowptr, A->colind,
-                           static_cast<const float*>(A->vals), L->rowptr, L->colind,
-                           with_vals ? static_cast<float*>(L->vals) : nullptr);
-      LSPCG_HIP(hipGetLastError());
-      LSPCG_HIP(hipStreamSynchronize(st));
-    }
-    (void)hipFree(tmp_rp);
-  }
-  (void)hipFree(cnt);
-  (void)hipFree(flag);
-  if (rc) {
-    if (L) lspcg_mat_destroy(L);
-    return rc;
-  }
-  *out = L;
+  if (int rc = B.get(&tmp_rp, n + 1)) return rc;
+  if (int rc = scan_to_rowptr(cnt, n, tmp_rp, &total, st)) return rc;
+  lspcg_mat* L = nullptr;
+  if (int rc = mat_alloc(A->ctx, n, total, 1, A->dtype, &L)) return rc;
+  MatGuard guard(L, lspcg_mat_destroy);
+  LSPCG_HIP(hipMemcpyAsync(L->rowptr, tmp_rp, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToDevice, st));
+  by_dtype(A->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_tril_fill<T>, dim3(fgrid(n)), dim3(kThreads), st, n, A->rowptr, A->colind, as<T>(A->vals), L->rowptr,
+           L->colind, with_vals ? as<T>(L->vals) : nullptr);
+  });
+  LSPCG_HIP(hipGetLastError());
+  LSPCG_HIP(hipStreamSynchronize(st));
+  *out = guard.release();
   return LSPCG_OK;
 }
 
@@ -182,19 +143,15 @@ __global__ void k_level_bounds(int64_t n, const int32_t* __restrict__ ls, int32_
 }
 
 void Levels::release() {
-  (void)hipFree(ptr);
   (void)hipFree(order);
-  (void)hipFree(pad);
-  (void)hipFree(head);
-  (void)hipFree(sv);
-  (void)hipFree(inv);
-  (void)hipFree(c);
-  sv = inv = c = nullptr;
-  ptr = order = pad = nullptr;
-  head = nullptr;
-  npad = 0;
+  order = nullptr;
   hptr.clear();
   nlev = 0;
+}
+
+void TrsvPlan::release() {
+  for (void* p : {(void*)pad, (void*)head, sv, inv, c}) (void)hipFree(p);
+  *this = TrsvPlan{};
 }
 
 // position t of the level-sorted order -> its place in the wave-padded order
@@ -206,25 +163,21 @@ __global__ void k_pad_order(int64_t n, const int32_t* __restrict__ lev_s, const 
   }
 }
 
-int build_levels(lspcg_ctx* ctx, int64_t n, const int32_t* rp, const int32_t* ci, bool lower, Levels* out) {
+// The level sort of n > 0 rows, in B's scratch: lev_s = the sorted levels, order = the rows by
+// (level, row), ptr (device) / hptr (host) = each level's first position
+struct LevelSort {
+  int32_t *lev_s = nullptr, *order = nullptr, *ptr = nullptr;
+  std::vector<int32_t> hptr;
+};
+
+static int sort_levels(lspcg_ctx* ctx, int64_t n, const int32_t* rp, const int32_t* ci, bool lower, DevBuf& B,
+                       LevelSort* S) {
   hipStream_t st = ctx->stream;
-  out->release();
-  if (n == 0) {
-    out->hptr = {0};
-    return LSPCG_OK;
-  }
   int32_t *lev = nullptr, *lev_s = nullptr, *iota = nullptr, *order = nullptr, *ptr = nullptr;
   int* changed = nullptr;
   void* tmp = nullptr;
   size_t tmp_bytes = 0;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)lev, (void*)lev_s, (void*)iota, (void*)changed, tmp}) (void)hipFree(p);
-  };
-  LSPCG_HIP(hipMalloc(&lev, sizeof(int32_t) * n));
-  LSPCG_HIP(hipMalloc(&lev_s, sizeof(int32_t) * n));
-  LSPCG_HIP(hipMalloc(&iota, sizeof(int32_t) * n));
-  LSPCG_HIP(hipMalloc(&order, sizeof(int32_t) * n));
-  LSPCG_HIP(hipMalloc(&changed, sizeof(int)));
+  if (int rc = B.get(&lev, n) | B.get(&lev_s, n) | B.get(&iota, n) | B.get(&order, n) | B.get(&changed, 1)) return rc;
   LSPCG_HIP(hipMemsetAsync(lev, 0, sizeof(int32_t) * n, st));
   // relaxation sweeps until a round of sweeps changes nothing (<= longest dependency chain + 1
   // sweeps); kSweepRound sweeps per host check of the flag (extra sweeps change nothing)
@@ -232,46 +185,61 @@ int build_levels(lspcg_ctx* ctx, int64_t n, const int32_t* rp, const int32_t* ci
   int h = 1;
   for (int64_t sweep = 0; h && sweep <= n; sweep += kSweepRound) {
     LSPCG_HIP(hipMemsetAsync(changed, 0, sizeof(int), st));
-    for (int r = 0; r < kSweepRound; ++r) {
-      if (lower)
-        hipLaunchKernelGGL(k_level_sweep<true>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, rp, ci, lev, changed);
-      else
-        hipLaunchKernelGGL(k_level_sweep<false>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, rp, ci, lev, changed);
-    }
-    LSPCG_HIP(hipMemcpyAsync(&h, changed, sizeof(int), hipMemcpyDeviceToHost, st));
-    LSPCG_HIP(hipStreamSynchronize(st));
+    for (int r = 0; r < kSweepRound; ++r)
+      by_flag(lower, [&](auto lo) {
+        launch(k_level_sweep<decltype(lo)::value>, dim3(fgrid(n)), dim3(kThreads), st, n, rp, ci, lev, changed);
+      });
+    if (int rc = flag_value(changed, st, &h)) return rc;
   }
-  hipLaunchKernelGGL(k_iota, dim3(fgrid(n)), dim3(kThreads), 0, st, n, iota);
+  launch(k_iota, dim3(fgrid(n)), dim3(kThreads), st, n, iota);
   LSPCG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, lev, lev_s, iota, order, int(n), 0, 32, st));
-  LSPCG_HIP(hipMalloc(&tmp, tmp_bytes));
+  if (int rc = B.get(&tmp, tmp_bytes)) return rc;
   LSPCG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, lev, lev_s, iota, order, int(n), 0, 32, st));
   int32_t maxl = 0;
-  LSPCG_HIP(hipMemcpyAsync(&maxl, lev_s + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (int rc = flag_value(lev_s + n - 1, st, &maxl)) return rc;
+  if (int rc = B.get(&ptr, maxl + 2)) return rc;
+  launch(k_level_bounds, dim3(fgrid(n)), dim3(kThreads), st, n, lev_s, ptr);
+  S->hptr.resize(maxl + 2);
+  LSPCG_HIP(hipMemcpyAsync(S->hptr.data(), ptr, sizeof(int32_t) * (maxl + 2), hipMemcpyDeviceToHost, st));
   LSPCG_HIP(hipStreamSynchronize(st));
-  LSPCG_HIP(hipMalloc(&ptr, sizeof(int32_t) * (maxl + 2)));
-  hipLaunchKernelGGL(k_level_bounds, dim3(fgrid(n)), dim3(kThreads), 0, st, n, lev_s, ptr);
-  out->hptr.resize(maxl + 2);
-  LSPCG_HIP(hipMemcpyAsync(out->hptr.data(), ptr, sizeof(int32_t) * (maxl + 2), hipMemcpyDeviceToHost, st));
-  LSPCG_HIP(hipStreamSynchronize(st));
-  // wave-padded order for the sync-free solve
-  std::vector<int32_t> pptr(maxl + 2, 0);
-  for (int l = 0; l <= maxl; ++l) pptr[l + 1] = pptr[l] + (out->hptr[l + 1] - out->hptr[l] + 63) / 64 * 64;
-  int32_t* dpptr = nullptr;
-  LSPCG_HIP(hipMalloc(&dpptr, sizeof(int32_t) * (maxl + 2)));
-  LSPCG_HIP(hipMemcpy(dpptr, pptr.data(), sizeof(int32_t) * (maxl + 2), hipMemcpyHostToDevice));
-  LSPCG_HIP(hipMalloc(&out->pad, sizeof(int32_t) * pptr[maxl + 1]));
-  LSPCG_HIP(hipMemsetAsync(out->pad, 0xFF, sizeof(int32_t) * pptr[maxl + 1], st));
-  hipLaunchKernelGGL(k_pad_order, dim3(fgrid(n)), dim3(kThreads), 0, st, n, lev_s, ptr, dpptr, order, out->pad);
-  LSPCG_HIP(hipMalloc(&out->head, 2 * sizeof(unsigned)));  // [dequeue counter | timeout flag]
-  LSPCG_HIP(hipMemsetAsync(out->head, 0, 2 * sizeof(unsigned), st));
-  LSPCG_HIP(hipStreamSynchronize(st));
-  (void)hipFree(dpptr);
-  out->npad = pptr[maxl + 1];
-  cleanup();
-  out->nlev = maxl + 1;
-  out->ptr = ptr;
-  out->order = order;
+  S->lev_s = lev_s;
+  S->order = order;
+  S->ptr = ptr;
   return LSPCG_OK;
+}
+
+int build_levels(lspcg_ctx* ctx, int64_t n, const int32_t* rp, const int32_t* ci, bool lower, Levels* out) {
+  out->release();
+  if (n == 0) {
+    out->hptr = {0};
+    return LSPCG_OK;
+  }
+  DevBuf B;
+  LevelSort S;
+  if (int rc = sort_levels(ctx, n, rp, ci, lower, B, &S)) return rc;
+  out->nlev = int(S.hptr.size()) - 1;
+  out->hptr = std::move(S.hptr);
+  out->order = B.keep(S.order);
+  return LSPCG_OK;
+}
+
+// Two-pointer merge of the sorted column lists ca[a..ae) and cb[b..be): on(a, b) at every common
+// column, in increasing column order (the oracle's order of operations)
+template <class F>
+__device__ __forceinline__ void merge_sorted(int a, int ae, const int32_t* ca, int b, int be, const int32_t* cb,
+                                             F on) {
+  while (a < ae && b < be) {
+    const int x = ca[a], y = cb[b];
+    if (x == y) {
+      on(a, b);
+      ++a;
+      ++b;
+    } else if (x < y) {
+      ++a;
+    } else {
+      ++b;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -289,20 +257,8 @@ __global__ void k_ic0_level(const int32_t* __restrict__ order, int32_t beg, int3
     const int k = ci[p];
     T s = L[p];
     // merge the already computed part of row i (columns < k) with row k (off-diagonal part)
-    int a = pb, b = rp[k];
     const int be = rp[k + 1] - 1;
-    while (a < p && b < be) {
-      const int ca = ci[a], cb = ci[b];
-      if (ca == cb) {
-        s = s - L[a] * L[b];
-        ++a;
-        ++b;
-      } else if (ca < cb) {
-        ++a;
-      } else {
-        ++b;
-      }
-    }
+    merge_sorted(pb, p, ci, rp[k], be, ci, [&](int a, int b) { s = s - L[a] * L[b]; });
     L[p] = s / L[be];
   }
   T s = L[pd];
@@ -463,81 +419,84 @@ __global__ void k_trsv_post(int64_t n, T* __restrict__ x, const T* __restrict__ 
   }
 }
 
-int trsv_prepare(const lspcg_mat* T_, bool lower, Levels* lv) {
+int trsv_plan_build(const lspcg_mat* T_, bool lower, TrsvPlan* out) {
   LSPCG_CHECK(T_->block_size == 1 && T_->storage_dtype() == T_->dtype, LSPCG_ERR_UNSUPPORTED,
               "trsv: scalar CSR with plain storage required");
+  out->release();
   hipStream_t st = T_->ctx->stream;
   const int64_t n = T_->n, nnz = T_->nnzb;
-  const size_t es = T_->dtype == LSPCG_F64 ? 8 : 4;
-  (void)hipFree(lv->sv);
-  (void)hipFree(lv->inv);
-  (void)hipFree(lv->c);
-  lv->sv = lv->inv = lv->c = nullptr;
-  LSPCG_HIP(hipMalloc(&lv->sv, es * std::max<int64_t>(nnz, 1)));
-  LSPCG_HIP(hipMalloc(&lv->inv, es * std::max<int64_t>(n, 1)));
-  LSPCG_HIP(hipMalloc(&lv->c, es * std::max<int64_t>(n, 1)));
   if (n == 0) return LSPCG_OK;
-  auto go = [&](auto tag) {
-    using T = decltype(tag);
-    auto v = static_cast<const T*>(T_->vals);
-    if (lower)
-      hipLaunchKernelGGL((k_trsv_inv<T, true>), dim3(fgrid(n)), dim3(kThreads), 0, st, n, T_->rowptr, v,
-                         static_cast<T*>(lv->inv), static_cast<T*>(lv->c));
-    else
-      hipLaunchKernelGGL((k_trsv_inv<T, false>), dim3(fgrid(n)), dim3(kThreads), 0, st, n, T_->rowptr, v,
-                         static_cast<T*>(lv->inv), static_cast<T*>(lv->c));
-    if (nnz)
-      hipLaunchKernelGGL(k_trsv_scale<T>, dim3(fgrid(nnz)), dim3(kThreads), 0, st, nnz, T_->colind, v,
-                         static_cast<const T*>(lv->inv), static_cast<T*>(lv->sv));
-  };
-  if (T_->dtype == LSPCG_F64) go(double{});
-  else go(float{});
-  LSPCG_HIP(hipGetLastError());
-  return LSPCG_OK;
-}
-
-int enqueue_trsv(const lspcg_mat* T_, const Levels& lv, bool lower, const void* b, void* x, const int32_t* done,
-                 hipStream_t st) {
-  if (lv.npad <= 0) return LSPCG_OK;
-  LSPCG_CHECK(lv.sv && lv.inv && lv.c, LSPCG_ERR_ARG, "trsv: levels not prepared (trsv_prepare)");
-  const int64_t n = T_->n;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  // 1 workgroup per CU (2 or 4 measured slower: more polling waves, DESIGN.md §6)
-  const dim3 g(unsigned(std::min<int64_t>((lv.npad + 255) / 256, int64_t(cus)))), blk(256);
-  LSPCG_HIP(hipMemsetAsync(lv.head, 0, sizeof(unsigned), st));
-  auto go = [&](auto tag) {
-    using T = decltype(tag);
-    auto vx = static_cast<T*>(x);
-    auto sv = static_cast<const T*>(lv.sv);
-    auto vb = static_cast<const T*>(b);
-    hipLaunchKernelGGL(k_trsv_wait_fill<T>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, vx, done);
-    if (lower) {
-      hipLaunchKernelGGL((k_trsv_syncfree<T, true>), g, blk, 0, st, lv.npad, lv.pad, T_->rowptr, T_->colind, sv, vb,
-                         vx, done, lv.head);
-      hipLaunchKernelGGL((k_trsv_post<T, true>), dim3(fgrid(n)), dim3(kThreads), 0, st, n, vx,
-                         static_cast<const T*>(lv.c), static_cast<const T*>(lv.inv), done);
-    } else {
-      hipLaunchKernelGGL((k_trsv_syncfree<T, false>), g, blk, 0, st, lv.npad, lv.pad, T_->rowptr, T_->colind, sv, vb,
-                         vx, done, lv.head);
-      hipLaunchKernelGGL((k_trsv_post<T, false>), dim3(fgrid(n)), dim3(kThreads), 0, st, n, vx,
-                         static_cast<const T*>(lv.c), static_cast<const T*>(lv.inv), done);
-    }
-  };
-  if (T_->dtype == LSPCG_F64) go(double{});
-  else go(float{});
-  LSPCG_HIP(hipGetLastError());
-  return LSPCG_OK;
-}
-
-int trsv_check_timeout(const Levels& lv, hipStream_t st) {
-  if (!lv.head) return LSPCG_OK;
-  unsigned h = 0;
-  LSPCG_HIP(hipMemcpyAsync(&h, lv.head + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  DevBuf B;
+  LevelSort S;
+  if (int rc = sort_levels(T_->ctx, n, T_->rowptr, T_->colind, lower, B, &S)) return rc;
+  // every level padded to whole wave64s
+  const int nlev = int(S.hptr.size()) - 1;
+  std::vector<int32_t> pptr(nlev + 1, 0);
+  for (int l = 0; l < nlev; ++l) pptr[l + 1] = pptr[l] + (S.hptr[l + 1] - S.hptr[l] + 63) / 64 * 64;
+  const int64_t npad = pptr[nlev];
+  int32_t *dpptr = nullptr, *pad = nullptr;
+  unsigned* head = nullptr;  // [dequeue counter | timeout flag]
+  if (int rc = B.get(&dpptr, nlev + 1) | B.get(&pad, npad) | B.get(&head, 2)) return rc;
+  LSPCG_HIP(hipMemcpy(dpptr, pptr.data(), sizeof(int32_t) * (nlev + 1), hipMemcpyHostToDevice));
+  LSPCG_HIP(hipMemsetAsync(pad, 0xFF, sizeof(int32_t) * npad, st));
+  launch(k_pad_order, dim3(fgrid(n)), dim3(kThreads), st, n, S.lev_s, S.ptr, dpptr, S.order, pad);
+  LSPCG_HIP(hipMemsetAsync(head, 0, 2 * sizeof(unsigned), st));
   LSPCG_HIP(hipStreamSynchronize(st));
+  out->pad = B.keep(pad);
+  out->npad = npad;
+  out->head = B.keep(head);
+  B.release();  // the sort's scratch, while nothing is enqueued
+  if (hipDeviceGetAttribute(&out->cus, hipDeviceAttributeMultiprocessorCount, T_->ctx->device) != hipSuccess ||
+      out->cus <= 0)
+    out->cus = 256;
+  // the scaled values: enqueued, not waited for
+  const int rc = by_dtype(T_->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    T *sv = nullptr, *inv = nullptr, *c = nullptr;
+    if (int rc = B.get(&sv, nnz) | B.get(&inv, n) | B.get(&c, n)) return rc;
+    out->sv = B.keep(sv);
+    out->inv = B.keep(inv);
+    out->c = B.keep(c);
+    by_flag(lower, [&](auto lo) {
+      launch(k_trsv_inv<T, decltype(lo)::value>, dim3(fgrid(n)), dim3(kThreads), st, n, T_->rowptr, as<T>(T_->vals),
+             inv, c);
+    });
+    if (nnz) launch(k_trsv_scale<T>, dim3(fgrid(nnz)), dim3(kThreads), st, nnz, T_->colind, as<T>(T_->vals), inv, sv);
+    LSPCG_HIP(hipGetLastError());
+    return LSPCG_OK;
+  });
+  if (rc) out->release();
+  return rc;
+}
+
+int enqueue_trsv(const lspcg_mat* T_, const TrsvPlan& plan, bool lower, const void* b, void* x, const int32_t* done,
+                 hipStream_t st) {
+  if (plan.npad <= 0) return LSPCG_OK;
+  const int64_t n = T_->n;
+  // 1 workgroup per CU (2 or 4 measured slower: more polling waves, DESIGN.md §6)
+  const dim3 g(unsigned(std::min<int64_t>((plan.npad + 255) / 256, int64_t(plan.cus)))), blk(256);
+  LSPCG_HIP(hipMemsetAsync(plan.head, 0, sizeof(unsigned), st));
+  by_dtype(T_->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_trsv_wait_fill<T>, dim3(fgrid(n)), dim3(kThreads), st, n, as<T>(x), done);
+    by_flag(lower, [&](auto lo) {
+      constexpr bool LOWER = decltype(lo)::value;
+      launch(k_trsv_syncfree<T, LOWER>, g, blk, st, plan.npad, plan.pad, T_->rowptr, T_->colind, as<T>(plan.sv),
+             as<T>(b), as<T>(x), done, plan.head);
+      launch(k_trsv_post<T, LOWER>, dim3(fgrid(n)), dim3(kThreads), st, n, as<T>(x), as<T>(plan.c), as<T>(plan.inv),
+             done);
+    });
+  });
+  LSPCG_HIP(hipGetLastError());
+  return LSPCG_OK;
+}
+
+int trsv_check_timeout(const TrsvPlan& plan, hipStream_t st) {
+  if (!plan.head) return LSPCG_OK;
+  int h = 0;
+  if (int rc = flag_value(reinterpret_cast<const int*>(plan.head + 1), st, &h)) return rc;
   if (h) {
-    LSPCG_HIP(hipMemsetAsync(lv.head + 1, 0, sizeof(unsigned), st));
+    LSPCG_HIP(hipMemsetAsync(plan.head + 1, 0, sizeof(unsigned), st));
     LSPCG_HIP(hipStreamSynchronize(st));
     set_error("triangular solve: a row waited more than 2 s for a dependency (sync-free hand-off timed out); "
               "the result is invalid");
@@ -550,39 +509,28 @@ int ic0_factor(const lspcg_mat* A, lspcg_mat** out) {
   LSPCG_CHECK(A && out, LSPCG_ERR_ARG, "ic0: NULL");
   hipStream_t st = A->ctx->stream;
   lspcg_mat* L = nullptr;
-  int rc = tril_of(A, true, &L);
-  if (rc) return rc;
+  if (int rc = tril_of(A, true, &L)) return rc;
+  MatGuard guard(L, lspcg_mat_destroy);
   Levels lv;
-  rc = build_levels(A->ctx, L->n, L->rowptr, L->colind, true, &lv);
+  if (int rc = build_levels(A->ctx, L->n, L->rowptr, L->colind, true, &lv)) return rc;
+  DevBuf B;
   int* flag = nullptr;
-  if (!rc && hipMalloc(&flag, sizeof(int)) != hipSuccess) rc = LSPCG_ERR_HIP;
-  if (!rc) {
-    (void)hipMemsetAsync(flag, 0, sizeof(int), st);
+  if (int rc = B.get(&flag, 1)) return rc;
+  LSPCG_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+  by_dtype(L->dtype, [&](auto t) {
+    using T = decltype(t);
     for (int l = 0; l < lv.nlev; ++l) {
       const int beg = lv.hptr[l], cnt = lv.hptr[l + 1] - lv.hptr[l];
-      const dim3 g((cnt + 127) / 128), blk(128);
-      if (L->dtype == LSPCG_F64)
-        hipLaunchKernelGGL(k_ic0_level<double>, g, blk, 0, st, lv.order, beg, cnt, L->rowptr, L->colind,
-                           static_cast<double*>(L->vals), flag);
-      else
-        hipLaunchKernelGGL(k_ic0_level<float>, g, blk, 0, st, lv.order, beg, cnt, L->rowptr, L->colind,
-                           static_cast<float*>(L->vals), flag);
+      launch(k_ic0_level<T>, dim3((cnt + 127) / 128), dim3(128), st, lv.order, beg, cnt, L->rowptr, L->colind,
+             as<T>(L->vals), flag);
     }
-    int f = 0;
-    if (hipGetLastError() != hipSuccess) rc = LSPCG_ERR_HIP;
-    if (!rc) rc = flag_value(flag, st, &f);
-    if (!rc && f) {
-      set_error("IC(0) breakdown: a non-positive pivot (the matrix is not an M-matrix / not SPD)");
-      rc = LSPCG_ERR_BREAKDOWN;
-    }
-  }
-  (void)hipFree(flag);
-  lv.release();
-  if (rc) {
-    lspcg_mat_destroy(L);
-    return rc;
-  }
-  *out = L;
+  });
+  LSPCG_HIP(hipGetLastError());
+  int f = 0;
+  if (int rc = flag_value(flag, st, &f)) return rc;
+  LSPCG_CHECK(!f, LSPCG_ERR_BREAKDOWN,
+              "IC(0) breakdown: a non-positive pivot (the matrix is not an M-matrix / not SPD)");
+  *out = guard.release();
   return LSPCG_OK;
 }
 
@@ -649,57 +597,14 @@ __global__ void k_ainv_level(const int32_t* __restrict__ order, int32_t beg, int
     const int i = cidx[c];
     // p = a_i . z_j over P_j (increasing k)
     T p = T(0);
-    {
-      int a = arp[i], q = pb;
-      const int ae = arp[i + 1];
-      while (a < ae && q < pe) {
-        const int ca = aci[a], cq = tci[q];
-        if (ca == cq) {
-          p = p + av[a] * z[q];
-          ++a;
-          ++q;
-        } else if (ca < cq) {
-          ++a;
-        } else {
-          ++q;
-        }
-      }
-    }
+    merge_sorted(arp[i], arp[i + 1], aci, pb, pe, tci, [&](int a, int q) { p = p + av[a] * z[q]; });
     if (p != T(0)) {
       const T f = p / d[i];
-      int a = trp[i], q = pb;
-      const int ae = trp[i + 1];
-      while (a < ae && q < pe) {
-        const int ca = tci[a], cq = tci[q];
-        if (ca == cq) {
-          z[q] = z[q] - f * z[a];
-          ++a;
-          ++q;
-        } else if (ca < cq) {
-          ++a;
-        } else {
-          ++q;
-        }
-      }
+      merge_sorted(trp[i], trp[i + 1], tci, pb, pe, tci, [&](int a, int q) { z[q] = z[q] - f * z[a]; });
     }
   }
   T dj = T(0);
-  {
-    int a = arp[j], q = pb;
-    const int ae = arp[j + 1];
-    while (a < ae && q < pe) {
-      const int ca = aci[a], cq = tci[q];
-      if (ca == cq) {
-        dj = dj + av[a] * z[q];
-        ++a;
-        ++q;
-      } else if (ca < cq) {
-        ++a;
-      } else {
-        ++q;
-      }
-    }
-  }
+  merge_sorted(arp[j], arp[j + 1], aci, pb, pe, tci, [&](int a, int q) { dj = dj + av[a] * z[q]; });
   if (!(dj > T(0))) {
     atomicOr(flag, 1);
     dj = T(1);
@@ -723,84 +628,48 @@ __global__ void k_ainv_scale(int64_t n, const int32_t* __restrict__ trp, const T
   }
 }
 
-template <typename T>
-static int ainv0_run(const lspcg_mat* A, lspcg_mat* Zt, const int32_t* cp, const int32_t* cidx, const Levels& lv,
-                     T* d, int* flag, hipStream_t st) {
-  const int64_t n = A->n;
-  T* z = static_cast<T*>(Zt->vals);
-  hipLaunchKernelGGL(k_ainv_init<T>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, Zt->rowptr, z);
-  for (int l = 0; l < lv.nlev; ++l) {
-    const int beg = lv.hptr[l], cnt = lv.hptr[l + 1] - lv.hptr[l];
-    hipLaunchKernelGGL(k_ainv_level<T>, dim3((cnt + 127) / 128), dim3(128), 0, st, lv.order, beg, cnt, A->rowptr,
-                       A->colind, static_cast<const T*>(A->vals), Zt->rowptr, Zt->colind, cp, cidx, z, d, flag);
-  }
-  hipLaunchKernelGGL(k_ainv_scale<T>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, Zt->rowptr, d, z);
-  LSPCG_HIP(hipGetLastError());
-  return LSPCG_OK;
-}
-
 int ainv0_factor(const lspcg_mat* A, lspcg_mat** out) {
   LSPCG_CHECK(A && out, LSPCG_ERR_ARG, "ainv0: NULL");
   LSPCG_CHECK(A->storage_dtype() == A->dtype, LSPCG_ERR_ARG, "ainv0: compact-storage views are not accepted");
   hipStream_t st = A->ctx->stream;
   const int64_t n = A->n;
   lspcg_mat* Zt = nullptr;  // rows = columns of Z (pattern tril(A)), scaled by d^{-1/2} at the end
-  int rc = tril_of(A, false, &Zt);
-  if (rc) return rc;
+  if (int rc = tril_of(A, false, &Zt)) return rc;
+  MatGuard guard(Zt, lspcg_mat_destroy);
+  DevBuf B;
+  Levels lv;
   int32_t *cnt = nullptr, *cp = nullptr, *cidx = nullptr;
   int* flag = nullptr;
-  void* d = nullptr;
-  Levels lv;
   int64_t total = 0;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)cnt, (void*)cp, (void*)cidx, (void*)flag, d}) (void)hipFree(p);
-    lv.release();
-  };
-  auto fail = [&](int code) {
-    cleanup();
-    lspcg_mat_destroy(Zt);
-    return code;
-  };
-  if (hipMalloc(&cnt, sizeof(int32_t) * std::max<int64_t>(n, 1)) != hipSuccess ||
-      hipMalloc(&cp, sizeof(int32_t) * (n + 1)) != hipSuccess || hipMalloc(&flag, sizeof(int)) != hipSuccess ||
-      hipMalloc(&d, (A->dtype == LSPCG_F64 ? 8 : 4) * std::max<int64_t>(n, 1)) != hipSuccess) {
-    set_error("ainv0: out of device memory");
-    return fail(LSPCG_ERR_HIP);
-  }
-  (void)hipMemsetAsync(flag, 0, sizeof(int), st);
-  hipLaunchKernelGGL(k_ainv_cand<false>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, A->rowptr, A->colind,
-                     Zt->rowptr, Zt->colind, cnt, static_cast<const int32_t*>(nullptr), static_cast<int32_t*>(nullptr),
-                     flag);
-  if ((rc = scan_to_rowptr(cnt, n, cp, &total, st))) return fail(rc);
-  if (hipMalloc(&cidx, sizeof(int32_t) * std::max<int64_t>(total, 1)) != hipSuccess) {
-    set_error("ainv0: out of device memory (candidate lists)");
-    return fail(LSPCG_ERR_HIP);
-  }
-  hipLaunchKernelGGL(k_ainv_cand<true>, dim3(fgrid(n)), dim3(kThreads), 0, st, n, A->rowptr, A->colind, Zt->rowptr,
-                     Zt->colind, cnt, cp, cidx, flag);
+  if (int rc = B.get(&cnt, n) | B.get(&cp, n + 1) | B.get(&flag, 1)) return rc;
+  LSPCG_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+  const dim3 g(fgrid(n)), blk(kThreads);
+  launch(k_ainv_cand<false>, g, blk, st, n, A->rowptr, A->colind, Zt->rowptr, Zt->colind, cnt, nullptr, nullptr, flag);
+  if (int rc = scan_to_rowptr(cnt, n, cp, &total, st)) return rc;
+  if (int rc = B.get(&cidx, total)) return rc;
+  launch(k_ainv_cand<true>, g, blk, st, n, A->rowptr, A->colind, Zt->rowptr, Zt->colind, cnt, cp, cidx, flag);
   int f = 0;
-  if ((rc = flag_value(flag, st, &f))) return fail(rc);
-  if (f & 2) {
-    set_error("ainv0: a row of tril(A) has more than 64 entries (unsupported)");
-    return fail(LSPCG_ERR_UNSUPPORTED);
-  }
-  if ((rc = build_levels(A->ctx, n, cp, cidx, true, &lv))) return fail(rc);
-  rc = A->dtype == LSPCG_F64
-           ? ainv0_run<double>(A, Zt, cp, cidx, lv, static_cast<double*>(d), flag, st)
-           : ainv0_run<float>(A, Zt, cp, cidx, lv, static_cast<float*>(d), flag, st);
-  if (rc) return fail(rc);
-  if ((rc = flag_value(flag, st, &f))) return fail(rc);
-  if (f & 1) {
-    set_error("AINV(0) breakdown: a non-positive pivot");
-    return fail(LSPCG_ERR_BREAKDOWN);
-  }
-  lspcg_mat* L = nullptr;  // L = (D^{-1/2} Zᵀ)ᵀ = Z D^{-1/2}
-  rc = lspcg_mat_transpose(Zt, &L);
-  cleanup();
-  lspcg_mat_destroy(Zt);
+  if (int rc = flag_value(flag, st, &f)) return rc;
+  LSPCG_CHECK(!(f & 2), LSPCG_ERR_UNSUPPORTED, "ainv0: a row of tril(A) has more than 64 entries (unsupported)");
+  if (int rc = build_levels(A->ctx, n, cp, cidx, true, &lv)) return rc;
+  const int rc = by_dtype(A->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    T *d = nullptr, *z = as<T>(Zt->vals);
+    if (int rc = B.get(&d, n)) return rc;
+    launch(k_ainv_init<T>, g, blk, st, n, Zt->rowptr, z);
+    for (int l = 0; l < lv.nlev; ++l) {
+      const int beg = lv.hptr[l], cnt_l = lv.hptr[l + 1] - lv.hptr[l];
+      launch(k_ainv_level<T>, dim3((cnt_l + 127) / 128), dim3(128), st, lv.order, beg, cnt_l, A->rowptr, A->colind,
+             as<T>(A->vals), Zt->rowptr, Zt->colind, cp, cidx, z, d, flag);
+    }
+    launch(k_ainv_scale<T>, g, blk, st, n, Zt->rowptr, d, z);
+    LSPCG_HIP(hipGetLastError());
+    return LSPCG_OK;
+  });
   if (rc) return rc;
-  *out = L;
-  return LSPCG_OK;
+  if (int rc2 = flag_value(flag, st, &f)) return rc2;
+  LSPCG_CHECK(!(f & 1), LSPCG_ERR_BREAKDOWN, "AINV(0) breakdown: a non-positive pivot");
+  return lspcg_mat_transpose(Zt, out);  // L = (D^{-1/2} Zᵀ)ᵀ = Z D^{-1/2}
 }
 
 }  // namespace lspcg
@@ -836,16 +705,15 @@ int lspcg_trsv(const lspcg_mat* T, int lower, const void* b, void* x) {
   LSPCG_CHECK(T->block_size == 1 && T->storage_dtype() == T->dtype, LSPCG_ERR_UNSUPPORTED,
               "trsv: scalar CSR with plain storage required");
   LSPCG_HIP(hipSetDevice(T->ctx->device));
-  Levels lv;
-  int rc = build_levels(T->ctx, T->n, T->rowptr, T->colind, lower != 0, &lv);
-  if (!rc) rc = trsv_prepare(T, lower != 0, &lv);
-  if (!rc) rc = enqueue_trsv(T, lv, lower != 0, b, x, nullptr, T->ctx->stream);
+  TrsvPlan plan;
+  int rc = trsv_plan_build(T, lower != 0, &plan);
+  if (!rc) rc = enqueue_trsv(T, plan, lower != 0, b, x, nullptr, T->ctx->stream);
   if (!rc && hipStreamSynchronize(T->ctx->stream) != hipSuccess) {
     set_error("trsv: stream synchronize failed");
     rc = LSPCG_ERR_HIP;
   }
-  if (!rc) rc = trsv_check_timeout(lv, T->ctx->stream);
-  lv.release();
+  if (!rc) rc = trsv_check_timeout(plan, T->ctx->stream);
+  plan.release();
   return rc;
 }
 

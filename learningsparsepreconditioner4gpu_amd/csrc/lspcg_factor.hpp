@@ -11,40 +11,49 @@
 
 namespace lspcg {
 
-// Rows grouped by dependency level: rows order[ptr[l] .. ptr[l+1]) form level l (ascending row
-// index inside a level); hptr is the host copy of ptr used to size the per-level launches.
+// Rows grouped by dependency level: rows order[hptr[l] .. hptr[l+1]) form level l (ascending row
+// index inside a level); hptr (host) sizes the per-level launches of the factorizations.
 struct Levels {
   int nlev = 0;
-  int32_t* ptr = nullptr;
   int32_t* order = nullptr;
   std::vector<int32_t> hptr;
-  // sync-free solve (lspcg_factor.hip k_trsv_syncfree): `order` with every level padded to whole
-  // wave64s (-1 = no row), so no wave holds two rows of which one waits for the other; npad
-  // positions; head[0] = the launch's block dequeue counter, head[1] = timeout flag
-  int32_t* pad = nullptr;
-  int64_t npad = 0;
-  unsigned* head = nullptr;
-  // the triangular factor's column-scaled values sv_p = v_p / d_col and per row inv = 1 / d,
-  // c = d inv (trsv_prepare: spsolve_triangular's scaling)
-  void* sv = nullptr;
-  void* inv = nullptr;
-  void* c = nullptr;
   void release();
+  Levels() = default;
+  Levels(const Levels&) = delete;
+  Levels& operator=(const Levels&) = delete;
+  ~Levels() { release(); }
 };
 
 // lower: row i depends on the columns j < i of its row; upper: on the columns j > i.
 int build_levels(lspcg_ctx* ctx, int64_t n, const int32_t* rp, const int32_t* ci, bool lower, Levels* out);
-// scaled values of T for enqueue_trsv (after build_levels), enqueued on T's context stream
-int trsv_prepare(const lspcg_mat* T, bool lower, Levels* lv);
+
+// What the sync-free solve with one triangular factor reads (lspcg_factor.hip k_trsv_syncfree).
+struct TrsvPlan {
+  // the level order with every level padded to whole wave64s (-1 = no row), so no wave holds two
+  // rows of which one waits for the other; npad positions
+  int32_t* pad = nullptr;
+  int64_t npad = 0;
+  unsigned* head = nullptr;  // head[0] = the launch's block dequeue counter, head[1] = timeout flag
+  // the factor's column-scaled values sv_p = v_p / d_col and per row inv = 1 / d, c = d inv
+  // (spsolve_triangular's scaling)
+  void* sv = nullptr;
+  void* inv = nullptr;
+  void* c = nullptr;
+  int cus = 0;  // the device's CU count (the resident grid's bound), queried when the plan is built
+  void release();
+};
+
+// levels of T, their padded order, the counter words and T's scaled values (replaces *out)
+int trsv_plan_build(const lspcg_mat* T, bool lower, TrsvPlan* out);
 // x = T⁻¹ b in scipy spsolve_triangular's arithmetic (lower: diagonal stored last in each row,
 // upper: first); `done` (nullable) is the solver's device done flag -- every launch returns at
 // once when it is set.  Counter reset + fill + one sync-free launch (rows wait for their
 // dependencies' values) + the diagonal scaling.
-int enqueue_trsv(const lspcg_mat* T, const Levels& lv, bool lower, const void* b, void* x, const int32_t* done,
+int enqueue_trsv(const lspcg_mat* T, const TrsvPlan& plan, bool lower, const void* b, void* x, const int32_t* done,
                  hipStream_t st);
 constexpr int kTrsvLaunches = 4;  // graph nodes one enqueue_trsv adds
-// LSPCG_ERR_HIP (and clears the flag) when a sync-free solve on these levels timed out
-int trsv_check_timeout(const Levels& lv, hipStream_t st);
+// LSPCG_ERR_HIP (and clears the flag) when a sync-free solve with this plan timed out
+int trsv_check_timeout(const TrsvPlan& plan, hipStream_t st);
 int ic0_factor(const lspcg_mat* A, lspcg_mat** L);
 int ainv0_factor(const lspcg_mat* A, lspcg_mat** L);
 

@@ -484,25 +484,15 @@ int lspcg_graph_create(lspcg_ctx* ctx, int64_t N, int64_t E, int bs, const int64
   int32_t* ids = nullptr;
   int* flag = nullptr;
   void* tmp = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)kr, (void*)kc, (void*)ks, (void*)ids, (void*)flag, tmp}) (void)hipFree(p);
-  };
-  struct Guard {
-    decltype(cleanup)& f;
-    ~Guard() { f(); }
-  } guard{cleanup};
-  LSPCG_HIP(hipMalloc(&kr, sizeof(uint64_t) * E));
-  LSPCG_HIP(hipMalloc(&kc, sizeof(uint64_t) * E));
-  LSPCG_HIP(hipMalloc(&ks, sizeof(uint64_t) * E));
-  LSPCG_HIP(hipMalloc(&ids, sizeof(int32_t) * E));
-  LSPCG_HIP(hipMalloc(&flag, sizeof(int)));
+  DevBuf B;
+  if (int rc = B.get(&kr, E) | B.get(&kc, E) | B.get(&ks, E) | B.get(&ids, E) | B.get(&flag, 1)) return rc;
   LSPCG_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_graph_keys, dim3(grid_of(E)), dim3(256), 0, st, E, N, edge_index, kr, kc, ids, flag);
   int bits = 1;
   while (bits < 64 && (uint64_t(1) << bits) < uint64_t(N) * uint64_t(N)) ++bits;
   size_t tb = 0;
   LSPCG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kr, ks, ids, g->rperm, int(E), 0, bits, st));
-  LSPCG_HIP(hipMalloc(&tmp, tb > 0 ? tb : 1));
+  if (int rc = B.get(&tmp, tb)) return rc;
   LSPCG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kr, ks, ids, g->rperm, int(E), 0, bits, st));
   hipLaunchKernelGGL(k_graph_ptr, dim3(grid_of(std::max<int64_t>(N + 1, E))), dim3(256), 0, st, E, N, ks, g->rp,
                      g->rother);
@@ -510,8 +500,7 @@ int lspcg_graph_create(lspcg_ctx* ctx, int64_t N, int64_t E, int bs, const int64
   hipLaunchKernelGGL(k_graph_ptr, dim3(grid_of(std::max<int64_t>(N + 1, E))), dim3(256), 0, st, E, N, ks, g->cp,
                      g->cother);
   int h = 0;
-  LSPCG_HIP(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  LSPCG_HIP(hipStreamSynchronize(st));
+  if (int rc = flag_value(flag, st, &h)) return rc;
   if (h) {
     lspcg_graph_destroy(g.release());
     set_error("graph_create: edge_index out of range [0, N)");

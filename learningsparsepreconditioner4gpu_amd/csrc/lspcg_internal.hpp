@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lspcg.h"
@@ -57,6 +58,7 @@ struct DevBuf {
     *out = static_cast<T*>(v);
     return LSPCG_OK;
   }
+  int get(void** out, size_t bytes) { return get(reinterpret_cast<char**>(out), bytes); }  // hipcub temp storage
   template <typename T>
   T* keep(T* v) {
     p.erase(std::remove(p.begin(), p.end(), static_cast<void*>(v)), p.end());
@@ -119,6 +121,29 @@ template <typename... P>
 inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st, typename arg_of<P>::type... args) {
   hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
 }
+
+// Run-time dtype / block size / flag -> compile-time tag of a generic lambda: f(T{}) with
+// T = double | float; f(T{}, integral_constant<int, 1 | 3>{}); f(bool_constant<b>{}).  Inside,
+// `using T = decltype(t);` and `constexpr int BS = decltype(bs)::value;`.
+template <class F>
+inline auto by_dtype(int dtype, F&& f) {
+  return dtype == LSPCG_F64 ? f(double{}) : f(float{});
+}
+template <class F>
+inline auto by_dtype_bs(int dtype, int bs, F&& f) {
+  return by_dtype(dtype, [&](auto t) {
+    return bs == 1 ? f(t, std::integral_constant<int, 1>{}) : f(t, std::integral_constant<int, 3>{});
+  });
+}
+template <class F>
+inline auto by_flag(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// the handles' untyped arrays as T
+template <typename T>
+inline T* as(void* p) { return static_cast<T*>(p); }
+template <typename T>
+inline const T* as(const void* p) { return static_cast<const T*>(p); }
 
 constexpr int kThreads = 256;       // 4 wave64 per workgroup
 constexpr int kElemBlocksMax = 2048;  // grid cap for streaming elementwise kernels
@@ -460,6 +485,11 @@ namespace lspcg {
 int mat_alloc_entries(lspcg_mat* m, int64_t nnzb);
 // New handle with rowptr[nb+1] and padded entry arrays (contents uninitialised).
 int mat_alloc(lspcg_ctx* ctx, int64_t nb, int64_t nnzb, int bs, int dtype, lspcg_mat** out);
+// host exclusive scan of the device counts cnt[0..n) into the device rowptr[0..n] (setup paths);
+// *total <- the sum, LSPCG_ERR_ARG when it does not fit an int32 index
+int scan_to_rowptr(const int32_t* cnt, int64_t n, int32_t* rowptr, int64_t* total, hipStream_t st);
+// *out <- the device int once the stream has drained
+int flag_value(const int* dflag, hipStream_t st, int* out);
 // lspcg_mat_transpose; *same_pattern (optional) <- the symmetric-pattern path ran, i.e. Aᵀ has
 // A's rowptr / colind and its values are a permutation of A's
 // reuse: an owned matrix of A's shape to overwrite instead of allocating (kept by the caller when

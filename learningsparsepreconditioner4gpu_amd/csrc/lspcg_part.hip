@@ -338,13 +338,11 @@ int lspcg_part_destroy(lspcg_part* p) {
 int lspcg_part_pack(lspcg_part* p, const void* v, void* sendbuf) {
   LSPCG_CHECK(p && v && (p->n_send == 0 || sendbuf), LSPCG_ERR_ARG, "part_pack: NULL argument");
   if (!p->n_send) return LSPCG_OK;
-  hipStream_t st = p->ctx->stream;
-  if (p->dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_part_pack<double>, dim3(part_grid(p->n_send)), dim3(kThreads), 0, st, p->n_send, p->send_idx,
-                       static_cast<const double*>(v), static_cast<double*>(sendbuf));
-  else
-    hipLaunchKernelGGL(k_part_pack<float>, dim3(part_grid(p->n_send)), dim3(kThreads), 0, st, p->n_send, p->send_idx,
-                       static_cast<const float*>(v), static_cast<float*>(sendbuf));
+  by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_part_pack<T>, dim3(part_grid(p->n_send)), dim3(kThreads), p->ctx->stream, p->n_send, p->send_idx,
+           as<T>(v), as<T>(sendbuf));
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -353,23 +351,23 @@ int lspcg_part_norms(lspcg_part* p, const void* a, const void* b, double* red) {
   LSPCG_CHECK(p && a && b && red, LSPCG_ERR_ARG, "part_norms: NULL argument");
   hipStream_t st = p->ctx->stream;
   LSPCG_HIP(hipMemsetAsync(red, 0, sizeof(double) * kPartGroups * 2 * 2, st));
-  const int g = part_grid(p->n_own);
-  if (p->dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_part_norms<double>, dim3(g), dim3(kThreads), 0, st, p->n_own, static_cast<const double*>(a),
-                       static_cast<const double*>(b), p->partials, p->ticket, red);
-  else
-    hipLaunchKernelGGL(k_part_norms<float>, dim3(g), dim3(kThreads), 0, st, p->n_own, static_cast<const float*>(a),
-                       static_cast<const float*>(b), p->partials, p->ticket, red);
+  by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_part_norms<T>, dim3(part_grid(p->n_own)), dim3(kThreads), st, p->n_own, as<T>(a), as<T>(b), p->partials,
+           p->ticket, red);
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
 
 int lspcg_part_lt(lspcg_part* p, const void* r_ext, void* t_ext) {
   LSPCG_CHECK(p && p->LT && r_ext && t_ext, LSPCG_ERR_ARG, "part_lt: NULL argument (or no L)");
-  EpiOwn<double> ed{static_cast<double*>(t_ext), p->n_own};
-  EpiOwn<float> ef{static_cast<float*>(t_ext), p->n_own};
-  ed.r0 = ef.r0 = p->r0;
-  int rc = p->dtype == LSPCG_F64 ? part_spmv<double>(p, p->LT, r_ext, ed) : part_spmv<float>(p, p->LT, r_ext, ef);
+  const int rc = by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    EpiOwn<T> e{as<T>(t_ext), p->n_own};
+    e.r0 = p->r0;
+    return part_spmv<T>(p, p->LT, r_ext, e);
+  });
   if (rc) return rc;
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
@@ -379,18 +377,12 @@ int lspcg_part_l(lspcg_part* p, const void* t_ext, const void* r, double eps, vo
   LSPCG_CHECK(p && p->L && t_ext && r && z && red, LSPCG_ERR_ARG, "part_l: NULL argument (or no L)");
   hipStream_t st = p->ctx->stream;
   LSPCG_HIP(hipMemsetAsync(red, 0, sizeof(double) * kPartGroups * 2 * 2, st));
-  int rc;
-  if (p->dtype == LSPCG_F64) {
-    EpiZPart<double> e{static_cast<double*>(z), static_cast<const double*>(r), eps, p->n_own, p->partials, p->ticket,
-                       red, 1};
+  const int rc = by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    EpiZPart<T> e{as<T>(z), as<T>(r), T(eps), p->n_own, p->partials, p->ticket, red, 1};
     e.r0 = p->r0;
-    rc = part_spmv<double>(p, p->L, t_ext, e);
-  } else {
-    EpiZPart<float> e{static_cast<float*>(z), static_cast<const float*>(r), float(eps), p->n_own, p->partials,
-                      p->ticket, red, 1};
-    e.r0 = p->r0;
-    rc = part_spmv<float>(p, p->L, t_ext, e);
-  }
+    return part_spmv<T>(p, p->L, t_ext, e);
+  });
   if (rc) return rc;
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
@@ -400,18 +392,12 @@ int lspcg_part_a(lspcg_part* p, const void* p_ext, void* q, double* red) {
   LSPCG_CHECK(p && p_ext && q && red, LSPCG_ERR_ARG, "part_a: NULL argument");
   hipStream_t st = p->ctx->stream;
   LSPCG_HIP(hipMemsetAsync(red, 0, sizeof(double) * kPartGroups * 2, st));
-  int rc;
-  if (p->dtype == LSPCG_F64) {
-    EpiQPart<double> e{static_cast<double*>(q), static_cast<const double*>(p_ext), p->n_own, p->partials, p->ticket,
-                       red, 1};
+  const int rc = by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    EpiQPart<T> e{as<T>(q), as<T>(p_ext), p->n_own, p->partials, p->ticket, red, 1};
     e.r0 = p->r0;
-    rc = part_spmv<double>(p, p->A, p_ext, e);
-  } else {
-    EpiQPart<float> e{static_cast<float*>(q), static_cast<const float*>(p_ext), p->n_own, p->partials, p->ticket,
-                      red, 1};
-    e.r0 = p->r0;
-    rc = part_spmv<float>(p, p->A, p_ext, e);
-  }
+    return part_spmv<T>(p, p->A, p_ext, e);
+  });
   if (rc) return rc;
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
@@ -420,13 +406,11 @@ int lspcg_part_a(lspcg_part* p, const void* p_ext, void* q, double* red) {
 int lspcg_part_update_p(lspcg_part* p, const void* z, void* p_ext, double beta, int first) {
   LSPCG_CHECK(p && z && p_ext, LSPCG_ERR_ARG, "part_update_p: NULL argument");
   hipStream_t st = p->ctx->stream;
-  const int g = part_grid(p->n_own);
-  if (p->dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_part_update_p<double>, dim3(g), dim3(kThreads), 0, st, p->n_own, static_cast<const double*>(z),
-                       static_cast<double*>(p_ext), beta, first);
-  else
-    hipLaunchKernelGGL(k_part_update_p<float>, dim3(g), dim3(kThreads), 0, st, p->n_own, static_cast<const float*>(z),
-                       static_cast<float*>(p_ext), float(beta), first);
+  by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_part_update_p<T>, dim3(part_grid(p->n_own)), dim3(kThreads), st, p->n_own, as<T>(z), as<T>(p_ext),
+           T(beta), first);
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -434,15 +418,11 @@ int lspcg_part_update_p(lspcg_part* p, const void* z, void* p_ext, double beta, 
 int lspcg_part_update_xr(lspcg_part* p, double alpha, const void* p_ext, const void* q, void* x, void* r_ext) {
   LSPCG_CHECK(p && p_ext && q && x && r_ext, LSPCG_ERR_ARG, "part_update_xr: NULL argument");
   hipStream_t st = p->ctx->stream;
-  const int g = part_grid(p->n_own);
-  if (p->dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_part_update_xr<double>, dim3(g), dim3(kThreads), 0, st, p->n_own, alpha,
-                       static_cast<const double*>(p_ext), static_cast<const double*>(q), static_cast<double*>(x),
-                       static_cast<double*>(r_ext));
-  else
-    hipLaunchKernelGGL(k_part_update_xr<float>, dim3(g), dim3(kThreads), 0, st, p->n_own, float(alpha),
-                       static_cast<const float*>(p_ext), static_cast<const float*>(q), static_cast<float*>(x),
-                       static_cast<float*>(r_ext));
+  by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_part_update_xr<T>, dim3(part_grid(p->n_own)), dim3(kThreads), st, p->n_own, T(alpha), as<T>(p_ext),
+           as<T>(q), as<T>(x), as<T>(r_ext));
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -461,11 +441,9 @@ int lspcg_part_state_init(lspcg_part* p, double rtol, int64_t max_iter, double* 
 int lspcg_part_scalars(lspcg_part* p, const double* gathered, int world, int phase) {
   LSPCG_CHECK(p && world >= 1 && phase >= kPartInit && phase <= kPartR && (gathered || phase == kPartZcg),
               LSPCG_ERR_ARG, "part_scalars: bad argument");
-  hipStream_t st = p->ctx->stream;
-  if (p->dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_part_scalars<double>, dim3(1), dim3(64), 0, st, p->S, gathered, world, phase);
-  else
-    hipLaunchKernelGGL(k_part_scalars<float>, dim3(1), dim3(64), 0, st, p->S, gathered, world, phase);
+  by_dtype(p->dtype, [&](auto t) {
+    launch(k_part_scalars<decltype(t)>, dim3(1), dim3(64), p->ctx->stream, p->S, gathered, world, phase);
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -473,13 +451,11 @@ int lspcg_part_scalars(lspcg_part* p, const double* gathered, int world, int pha
 int lspcg_part_update_p_dev(lspcg_part* p, const void* z, void* p_ext) {
   LSPCG_CHECK(p && z && p_ext, LSPCG_ERR_ARG, "part_update_p_dev: NULL argument");
   hipStream_t st = p->ctx->stream;
-  const int g = part_grid(p->n_own);
-  if (p->dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_part_update_p_dev<double>, dim3(g), dim3(kThreads), 0, st, p->n_own, p->S,
-                       static_cast<const double*>(z), static_cast<double*>(p_ext));
-  else
-    hipLaunchKernelGGL(k_part_update_p_dev<float>, dim3(g), dim3(kThreads), 0, st, p->n_own, p->S,
-                       static_cast<const float*>(z), static_cast<float*>(p_ext));
+  by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_part_update_p_dev<T>, dim3(part_grid(p->n_own)), dim3(kThreads), st, p->n_own, p->S, as<T>(z),
+           as<T>(p_ext));
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -487,15 +463,11 @@ int lspcg_part_update_p_dev(lspcg_part* p, const void* z, void* p_ext) {
 int lspcg_part_update_xr_dev(lspcg_part* p, const void* p_ext, const void* q, void* x, void* r_ext) {
   LSPCG_CHECK(p && p_ext && q && x && r_ext, LSPCG_ERR_ARG, "part_update_xr_dev: NULL argument");
   hipStream_t st = p->ctx->stream;
-  const int g = part_grid(p->n_own);
-  if (p->dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_part_update_xr_dev<double>, dim3(g), dim3(kThreads), 0, st, p->n_own, p->S,
-                       static_cast<const double*>(p_ext), static_cast<const double*>(q), static_cast<double*>(x),
-                       static_cast<double*>(r_ext));
-  else
-    hipLaunchKernelGGL(k_part_update_xr_dev<float>, dim3(g), dim3(kThreads), 0, st, p->n_own, p->S,
-                       static_cast<const float*>(p_ext), static_cast<const float*>(q), static_cast<float*>(x),
-                       static_cast<float*>(r_ext));
+  by_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_part_update_xr_dev<T>, dim3(part_grid(p->n_own)), dim3(kThreads), st, p->n_own, p->S, as<T>(p_ext),
+           as<T>(q), as<T>(x), as<T>(r_ext));
+  });
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }

@@ -322,8 +322,8 @@ static int enqueue_iteration(lspcg_solver* s, hipStream_t st) {
     case LSPCG_PRECOND_IC: {
       // z = L⁻ᵀ L⁻¹ r (t holds L⁻¹ r), ρ = r·z; then the top-of-loop test in the p update
       const int32_t* done = &S->done;
-      if ((rc = enqueue_trsv(s->icL, s->levL, true, r, t, done, st))) return rc;
-      if ((rc = enqueue_trsv(s->icU, s->levU, false, t, z, done, st))) return rc;
+      if ((rc = enqueue_trsv(s->icL, s->planL, true, r, t, done, st))) return rc;
+      if ((rc = enqueue_trsv(s->icU, s->planU, false, t, z, done, st))) return rc;
       hipLaunchKernelGGL(k_dot_rho<T>, dim3(eg), dim3(kThreads), 0, st, n, S, static_cast<const T*>(r),
                          static_cast<const T*>(z), s->partials, s->ticket);
       enqueue_ob<kObRho>(s, st, 1, r, z);
@@ -719,16 +719,14 @@ static int install_ic(lspcg_solver* s, const lspcg_mat* given, double* t_prec_ms
     if (*m) lspcg_mat_destroy(*m);
     *m = nullptr;
   }
-  s->levL.release();
-  s->levU.release();
+  s->planL.release();
+  s->planU.release();
   int rc = given ? lspcg_mat_create_csr(s->ctx, given->n, given->nnzb, given->rowptr, given->colind, given->vals,
                                         given->dtype, &s->icL)
                  : ic0_factor(s->A, &s->icL);
   if (!rc) rc = lspcg_mat_transpose(s->icL, &s->icU);
-  if (!rc) rc = build_levels(s->ctx, s->n, s->icL->rowptr, s->icL->colind, true, &s->levL);
-  if (!rc) rc = build_levels(s->ctx, s->n, s->icU->rowptr, s->icU->colind, false, &s->levU);
-  if (!rc) rc = trsv_prepare(s->icL, true, &s->levL);
-  if (!rc) rc = trsv_prepare(s->icU, false, &s->levU);
+  if (!rc) rc = trsv_plan_build(s->icL, true, &s->planL);
+  if (!rc) rc = trsv_plan_build(s->icU, false, &s->planU);
   if (rc) return rc;
   LSPCG_HIP(hipEventRecord(s->ev_t1, cst));
   LSPCG_HIP(hipEventSynchronize(s->ev_t1));
@@ -822,10 +820,10 @@ int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int
   if (ic) {
     if (!s->hflags) LSPCG_HIP(hipHostMalloc(&s->hflags, 2 * sizeof(unsigned), hipHostMallocDefault));
     s->hflags[0] = s->hflags[1] = 0;
-    if (s->levL.head)
-      LSPCG_HIP(hipMemcpyAsync(&s->hflags[0], s->levL.head + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    if (s->levU.head)
-      LSPCG_HIP(hipMemcpyAsync(&s->hflags[1], s->levU.head + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    if (s->planL.head)
+      LSPCG_HIP(hipMemcpyAsync(&s->hflags[0], s->planL.head + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    if (s->planU.head)
+      LSPCG_HIP(hipMemcpyAsync(&s->hflags[1], s->planU.head + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   }
   const SolveTail tail(fin, max_iter);
   if (res_hist) LSPCG_HIP(hipMemcpyAsync(s->hhist, dhist, sizeof(double) * tail.written, hipMemcpyDeviceToHost, st));
@@ -835,8 +833,8 @@ int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int
   LSPCG_HIP(hipEventSynchronize(s->ev_out));
   if (ic && (s->hflags[0] || s->hflags[1])) {  // a timed-out sync-free hand-off fails the solve loudly
     sub.lock();
-    if (int r2 = trsv_check_timeout(s->levL, st)) return r2;  // resets the flag, sets the message
-    if (int r2 = trsv_check_timeout(s->levU, st)) return r2;
+    if (int r2 = trsv_check_timeout(s->planL, st)) return r2;  // resets the flag, sets the message
+    if (int r2 = trsv_check_timeout(s->planU, st)) return r2;
   }
   float ms = 0.f;
   LSPCG_HIP(hipEventElapsedTime(&ms, s->ev_t0, s->ev_t1));
@@ -978,8 +976,8 @@ int lspcg_solver_destroy(lspcg_solver* s) {
   s->ro.release();
   if (s->icL) lspcg_mat_destroy(s->icL);
   if (s->icU) lspcg_mat_destroy(s->icU);
-  s->levL.release();
-  s->levU.release();
+  s->planL.release();
+  s->planU.release();
   for (void* p : {s->own_A, s->own_L, s->own_LT}) (void)hipFree(p);
   for (int w = 0; w < 3; ++w) {
     (void)hipFree(s->sv[w]);

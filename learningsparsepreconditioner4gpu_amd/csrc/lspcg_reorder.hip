@@ -110,9 +110,9 @@ void Reorder::release() {
 
 int mean_abs_offset(const lspcg_mat* A, double* out) {
   hipStream_t st = A->ctx->stream;
+  DevBuf B;
   unsigned long long* d = nullptr;
-  LSPCG_HIP(hipMalloc(&d, sizeof(unsigned long long)));
-  std::unique_ptr<unsigned long long, void (*)(unsigned long long*)> guard(d, [](unsigned long long* p) { (void)hipFree(p); });
+  if (int rc = B.get(&d, 1)) return rc;
   LSPCG_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), st));
   if (A->nb > 0)
     hipLaunchKernelGGL(k_abs_offset_sum, dim3(grid_for(A->nb)), dim3(kThreads), 0, st, A->nb, A->rowptr, A->colind, d);
@@ -661,17 +661,15 @@ int rcm_reorder(const lspcg_mat* A, int mode, Reorder* out, bool* applied) {
     return rc == kRcmSkip ? LSPCG_OK : rc;
   }
   {
+    DevBuf B;
     unsigned long long* d = nullptr;
-    LSPCG_HIP(hipMalloc(&d, sizeof(unsigned long long)));
+    if (int rc = B.get(&d, 1)) return rc;
     LSPCG_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_abs_offset_perm, dim3(grid_for(nb)), dim3(kThreads), 0, st, nb, A->rowptr, A->colind,
                        out->iperm, d);
     unsigned long long h = 0;
-    const hipError_t e1 = hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d);
-    LSPCG_HIP(e1);
-    LSPCG_HIP(e2);
+    LSPCG_HIP(hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, st));
+    LSPCG_HIP(hipStreamSynchronize(st));
     out->off_after = double(h) / double(A->nnzb);
   }
   if (mode < 0 && !(out->off_after < 0.5 * before)) {  // RCM would not help this pattern
@@ -698,15 +696,14 @@ int mat_permute(const lspcg_mat* M, const Reorder& R, lspcg_mat** out, lspcg_mat
   std::unique_ptr<lspcg_mat, int (*)(lspcg_mat*)> guard(reuse ? nullptr : P, lspcg_mat_destroy);
   P->val_dtype = M->val_dtype;
   const int64_t nb = M->nb;
+  DevBuf B;
   int32_t* len = nullptr;
-  LSPCG_HIP(hipMalloc(&len, sizeof(int32_t) * (nb + 1)));
-  std::unique_ptr<int32_t, void (*)(int32_t*)> lguard(len, [](int32_t* p) { (void)hipFree(p); });
+  if (int rc = B.get(&len, nb + 1)) return rc;
   hipLaunchKernelGGL(k_perm_len, dim3(grid_for(nb + 1)), dim3(kThreads), 0, st, nb, M->rowptr, R.perm, len);
   size_t tb = 0;
   LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, len, P->rowptr, int(nb + 1), st));
   void* tmp = nullptr;
-  LSPCG_HIP(hipMalloc(&tmp, tb ? tb : 1));
-  std::unique_ptr<void, void (*)(void*)> tguard(tmp, [](void* p) { (void)hipFree(p); });
+  if (int rc = B.get(&tmp, tb)) return rc;
   LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, len, P->rowptr, int(nb + 1), st));
   const int bb = M->block_size * M->block_size;
   const int g = grid_for(nb * 64);

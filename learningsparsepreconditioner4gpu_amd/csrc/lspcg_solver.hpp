@@ -111,10 +111,10 @@ struct lspcg_solver {
   void* own_LT = nullptr;
   int64_t own_L_n = -1, own_LT_n = -1;  // entries of the fp32 copies above (refilled in place)
   int* flag = nullptr;
-  // IC(0): factor, its explicit transpose and their level sets
+  // IC(0): factor, its explicit transpose and their sync-free solve plans
   lspcg_mat* icL = nullptr;
   lspcg_mat* icU = nullptr;
-  lspcg::Levels levL, levU;
+  lspcg::TrsvPlan planL, planU;
   // SELL-64 copies of the scalar iteration views A (0), L (1), Lᵀ (2) (lspcg_sell.hpp); sp[w]
   // is null where the CSR kernel is used (block size 3, irregular rows, LSPCG_NO_SELL=1)
   bool use_sell = true;

@@ -114,6 +114,45 @@ def test_ic0_breakdown_is_reported(gpu_ctx):
     assert e.value.code == _lib.ERR_BREAKDOWN
 
 
+def test_setup_paths_hold_device_memory_steady(gpu_ctx):
+    """ic0 / ainv0 / trsv / the general transpose path and one reported breakdown, 40 rounds after
+    a 20-round warm-up, leave the device's free memory where it was: every scratch array of the
+    setup paths (64 KB int32 arrays at ~16 k rows) is freed on success and on a reported failure."""
+    from learningsparsepreconditioner4gpu_amd import _lib
+
+    A1, m1, _ = P.poisson2d_grid(128, 128)
+    A = _masked(A1, m1)
+    dA = _dm(A)
+    L = OP.ic0(A)
+    U = sp.csr_matrix(L.T)
+    U.sort_indices()
+    dL, dU, dT = _dm(L), _dm(U), _dm(sp.csr_matrix(sp.tril(A)))
+    bad = _dm(sp.csr_matrix(np.array([[1.0, 2.0], [2.0, 1.0]])))
+    r = torch.from_numpy(np.random.default_rng(3).normal(size=A.shape[0])).cuda()
+    x = torch.empty_like(r)
+
+    def one_round():
+        dA.ic0()
+        dA.ainv0()
+        dL.trsv(r, lower=True, out=x)
+        dU.trsv(r, lower=False, out=x)
+        dT.transpose()
+        with pytest.raises(_lib.LspcgError) as e:
+            bad.ic0()
+        assert e.value.code == _lib.ERR_BREAKDOWN
+
+    for _ in range(20):
+        one_round()
+    torch.cuda.synchronize()
+    before = torch.cuda.mem_get_info()[0]
+    for _ in range(40):
+        one_round()
+    torch.cuda.synchronize()
+    after = torch.cuda.mem_get_info()[0]
+    print("free bytes after warm-up", before, "after 40 more rounds", after)
+    assert after >= before
+
+
 def test_ic_concurrent_solves_match_sequential(gpu_ctx):
     """Sync-free IC triangular solves under contention: four PCG-IC solves in flight on separate
     streams (linalg.solve_many: the solves' resident grids share the CUs and the hardware queues,
