@@ -224,21 +224,33 @@ int lspcg_solver_reorder_info(const lspcg_solver* s, int* applied, double* mean_
                               double* mean_offset_after);
 int lspcg_solver_destroy(lspcg_solver* s);
 
-/* ---- batched lockstep ext_spai PCG over independent systems (infer.py:278-331 solves its samples
- * one after another, each a get_pcg_iter_time call, validate.py:89-121; this solves a window of
- * them with every launch covering all systems -- DESIGN.md §6).  Each system keeps scipy cg's
- * recurrence, its own scalars, top-of-loop test and iteration count: the result per system is
- * what lspcg_solver_solve returns for it alone (count and history equal; iterate within the
- * compensated dots' rounding, same bits in practice).  A[k], L[k]: nsys >= 1 matrices of one
- * dtype and block size (L[k] the ext_spai factor of A[k]); the handles must outlive the batch
- * only until lspcg_batch_create returns (their entries are copied into a block-diagonal system
- * whose per-system row ranges are padded to whole 256-row workgroup tiles).
+/* ---- batched lockstep PCG over independent systems (infer.py:278-331 solves its samples one
+ * after another, each a get_pcg_iter_time / get_cg_iter_time call, validate.py:54-160; this solves
+ * a window of them with every launch covering all systems -- DESIGN.md §6).  Each system keeps
+ * scipy cg's recurrence, its own scalars, top-of-loop test and iteration count: the result per
+ * system is what lspcg_solver_solve returns for it alone with the same preconditioner kind (count,
+ * status and history equal; iterate within the compensated dots' rounding, same bits in practice).
+ * A[k], L[k]: nsys >= 1 matrices of one dtype and block size (L[k] the ext_spai factor of A[k]);
+ * the handles must outlive the batch only until the create call returns (their entries are copied
+ * into a block-diagonal system whose per-system row ranges are padded to whole 256-row workgroup
+ * tiles; padding rows are empty, stay 0 in every vector and get d = 1 where a kind divides by
+ * diag(A)).
  * Windows whose systems all fit the one-workgroup solve (n <= 2560 in fp64) run it with one
- * workgroup per system in one launch; others run the five phases in lockstep.
- * LSPCG_ERR_UNSUPPORTED when a SELL view cannot be built (irregular rows): solve one by one. */
+ * workgroup per system in one launch; others run the phases in lockstep: five launches per
+ * iteration (KA, KB, UP, KC, UR) for the two ext_spai kinds, three (UP, KC, UR -- UR also reduces
+ * the next iteration's dots per system) for none / diagonal.
+ * LSPCG_ERR_UNSUPPORTED when a SELL view cannot be built (irregular rows): solve one by one.
+ *
+ * lspcg_batch_create_precond: precond is LSPCG_PRECOND_NONE, _DIAGONAL, _EXT_SPAI or
+ * _EXT_SPAI_SCALED; LSPCG_PRECOND_IC returns LSPCG_ERR_UNSUPPORTED (triangular solves do not fit
+ * the tile-per-workgroup scheme).  L is required for the two ext_spai kinds (L[k] of A[k]'s size)
+ * and must be NULL for none / diagonal, where epsilon is ignored.  lspcg_batch_create is the
+ * LSPCG_PRECOND_EXT_SPAI case. */
 typedef struct lspcg_batch lspcg_batch;
 int lspcg_batch_create(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, const lspcg_mat* const* L,
                        double epsilon, lspcg_batch** out);
+int lspcg_batch_create_precond(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, const lspcg_mat* const* L,
+                               int precond, double epsilon, lspcg_batch** out);
 /* b[k], x[k]: device vectors of system k (x in: x0, out: solution).  max_iter <= 0: each
  * system's own n.  iters[k], status[k] (LSPCG_OK converged / LSPCG_NOT_CONVERGED) per system;
  * res_hist (nullable): per-system host arrays of length max_iter_k + 2 (or NULL entries);

@@ -77,6 +77,7 @@ SIGNATURES = {
     "lspcg_solver_set_dot_order": (C.c_int, [vp, C.c_int, C.c_int]),
     "lspcg_solver_destroy": (C.c_int, [vp]),
     "lspcg_batch_create": (C.c_int, [vp, C.c_int, pp, pp, C.c_double, pp]),
+    "lspcg_batch_create_precond": (C.c_int, [vp, C.c_int, pp, pp, C.c_int, C.c_double, pp]),
     "lspcg_batch_solve": (C.c_int, [vp, pp, pp, C.c_double, C.c_int64, p_i64, p_i32, C.POINTER(p_f64), p_f64]),
     "lspcg_batch_destroy": (C.c_int, [vp]),
     "lspcg_assemble": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int,

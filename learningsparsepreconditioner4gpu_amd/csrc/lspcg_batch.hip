@@ -1,7 +1,10 @@
-// ==== batched lockstep ext_spai PCG (lspcg_batch_*) ===========================
+// ==== batched lockstep PCG (lspcg_batch_*) =====================================
 // A window of independent systems is laid out block-diagonally, every system's rows padded to
-// whole SpMV row tiles (256 block rows), and ONE launch per phase covers all of them: the split
-// schedule's five launches (KA, KB, UP, KC, UR) with
+// whole SpMV row tiles (256 block rows), and ONE launch per phase covers all of them.  The two
+// ext_spai kinds run the split schedule's five launches (KA, KB, UP, KC, UR; the scaled kind with
+// EpiT / EpiZ's divisions by d = diag(A)); no preconditioner and the diagonal one have no KA / KB
+// and run three (UP, KC, UR), UR also reducing the next iteration's dots (‖r‖², ρ = r·z) per
+// system.  In every launch
 //   * one row tile per workgroup (launch_spmv_sell_cfg one_tile_per_wg), so a workgroup's dot
 //     partial is its tile's and its prologue tests the tile's own system (done systems' tiles
 //     leave at once);
@@ -9,8 +12,11 @@
 //     finish KB / KC sums the system's tile partials and updates its PcgState (scipy's scalars,
 //     the top-of-loop test, the iteration count), as the last-arriver schedule does for one system;
 //   * elementwise launches (UP, UR) of one 256-row tile per workgroup that read their system's
-//     finished scalars.
-// Padding rows are empty: they stay 0 in every vector and add exact zeros to the dots.
+//     finished scalars; the three-launch UR reduces per system over ELEMENTWISE tiles (bs per SpMV
+//     tile), with tickets and partials of its own sized for that launch.
+// Padding rows are empty: they stay 0 in every vector and add exact zeros to the dots; the kinds
+// that divide by d give them d = 1 at creation (k_batch_pad_d), since diag(A) is 0 there and 0/0
+// would put NaN into the system's dots.
 //
 // The window is solved by an lspcg_solver of the block-diagonal system (lspcg_solver.hpp, created
 // in lspcg_pcg.hip); the loop's shared device code is in lspcg_pcg_kernels.hpp.
@@ -49,15 +55,16 @@ struct ProTile {
 // system's few hundred -- the fan-in price), and the system's last arriving tile sums the system's
 // tile totals in tile order (fixed tree: the result does not depend on which tile came last);
 // thread 0 then runs fin(sys, values).  The elementwise launches read finished per-system scalars.
+// sys_reduce_tiles is the reduction itself over tiles [t0, t0 + nt) of system `sys` in the launch's
+// own tile numbering (SpMV row tiles, or elementwise tiles for the three-launch UR), `top` the
+// system's first ticket line for that launch.
 template <int N, class Fin>
-__device__ __forceinline__ void batch_sys_reduce(DD (&v)[N], double* partials, unsigned* tickets, const BatchMap& m,
+__device__ __forceinline__ void sys_reduce_tiles(DD (&v)[N], double* partials, unsigned* top, int sys, int t0, int nt,
                                                  Fin fin) {
   __shared__ DD lds[16 * N];
   __shared__ int s_last;
   block_reduce_dd<N>(v, lds);
   const int64_t tile = blockIdx.x;
-  const int sys = m.etile_sys[tile * m.bs];
-  const int t0 = m.tile0[sys], nt = m.tile0[sys + 1] - t0;
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -65,7 +72,6 @@ __device__ __forceinline__ void batch_sys_reduce(DD (&v)[N], double* partials, u
       st_agent_f64(&partials[(size_t(tile) * N + j) * 2 + 1], v[j].c);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned* top = tickets + size_t(kTicketStride) * m.tk0[sys];
     const unsigned g = unsigned(tile - t0) / kTicketGroup;
     const unsigned gsize = min(unsigned(kTicketGroup), unsigned(nt) - g * kTicketGroup);
     const unsigned ng = (unsigned(nt) + kTicketGroup - 1) / kTicketGroup;
@@ -100,10 +106,45 @@ __device__ __forceinline__ void batch_sys_reduce(DD (&v)[N], double* partials, u
   }
 }
 
-// init: r_0 = b - A x0 ; ‖r_0‖², ‖b‖² -> the system's initial state (EpiResid::fin)
+template <int N, class Fin>
+__device__ __forceinline__ void batch_sys_reduce(DD (&v)[N], double* partials, unsigned* tickets, const BatchMap& m,
+                                                 Fin fin) {
+  const int sys = m.etile_sys[int64_t(blockIdx.x) * m.bs];
+  const int t0 = m.tile0[sys];
+  sys_reduce_tiles<N>(v, partials, tickets + size_t(kTicketStride) * m.tk0[sys], sys, t0, m.tile0[sys + 1] - t0, fin);
+}
+
+// scipy's top-of-loop test for a system at iteration k with ‖r_k‖² = rr (ProCheck's codes)
 template <typename T>
+__device__ __forceinline__ int loop_test(int64_t k, int64_t max_iter, double rr, double atol) {
+  if (k >= max_iter) return 2;
+  const double rn = double(tsqrt<T>(T(rr)));
+  if (rn < atol) return 1;
+  if (!(rn == rn) || rn == INFINITY) return 3;
+  return 0;
+}
+
+// the system's initial state from its init dots ‖r_0‖², ‖b‖² (, ρ_0 = r_0·z_0 for Jacobi): EpiResid::fin
+template <typename T, int PRE>
+__device__ __forceinline__ void init_state(PcgState* St, const double* v) {
+  St->rr = round_to<T>(v[0]);
+  St->bb = round_to<T>(v[1]);
+  const double bn = double(tsqrt<T>(T(St->bb)));
+  St->atol = fmax(0.0, St->rtol * bn);
+  St->rho = PRE == LSPCG_PRECOND_DIAGONAL ? round_to<T>(v[2]) : St->rr;
+  St->alpha = 0.0;
+  St->iter = 0;
+  St->done = (bn == 0.0) ? 1 : 0;
+  if (St->hist) St->hist[0] = double(tsqrt<T>(T(St->rr)));
+}
+
+// init: r_0 = b - A x0 ; ‖r_0‖², ‖b‖² -> the system's initial state (EpiResid::fin).  PRE = NONE /
+// DIAGONAL (three-launch schedule): Jacobi's z_0 = r_0/d and ρ_0 as EpiResid<T, DIAGONAL>, and the
+// last arriver also runs iteration 0's top-of-loop test, which the ext_spai kinds leave to KB
+template <typename T, int PRE = LSPCG_PRECOND_EXT_SPAI>
 struct EpiResidB {
-  static constexpr int NDOT = 2;
+  static constexpr bool CG = PRE == LSPCG_PRECOND_NONE || PRE == LSPCG_PRECOND_DIAGONAL;
+  static constexpr int NDOT = PRE == LSPCG_PRECOND_DIAGONAL ? 3 : 2;
   static constexpr bool CUSTOM_FINISH = true;
   T* r;
   const T* b;
@@ -111,6 +152,8 @@ struct EpiResidB {
   double* partials;
   unsigned* tickets;
   BatchMap m;
+  const T* d = nullptr;
+  T* z = nullptr;
   __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
     const T bi = gld(b + i);
@@ -118,28 +161,32 @@ struct EpiResidB {
     gst(r + i, ri);
     dd_fma(dots[0], double(ri), double(ri));
     dd_fma(dots[1], double(bi), double(bi));
+    if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
+      const T zi = ri / gld(d + i);
+      gst(z + i, zi);
+      dd_fma(dots[2], double(ri), double(zi));
+    }
   }
-  __device__ __forceinline__ void finish(DD (&d)[2]) const {
+  __device__ __forceinline__ void finish(DD (&dd)[NDOT]) const {
     PcgState* Sb = S;
-    batch_sys_reduce<2>(d, partials, tickets, m, [Sb](int sys, const double* v) {
+    batch_sys_reduce<NDOT>(dd, partials, tickets, m, [Sb](int sys, const double* v) {
       PcgState* St = Sb + sys;
-      St->rr = round_to<T>(v[0]);
-      St->bb = round_to<T>(v[1]);
-      const double bn = double(tsqrt<T>(T(St->bb)));
-      St->atol = fmax(0.0, St->rtol * bn);
-      St->rho = St->rr;
-      St->alpha = 0.0;
-      St->iter = 0;
-      St->done = (bn == 0.0) ? 1 : 0;
-      if (St->hist) St->hist[0] = double(tsqrt<T>(T(St->rr)));
+      init_state<T, PRE>(St, v);
+      if constexpr (CG) {
+        if (!St->done) {
+          const int code = loop_test<T>(0, St->max_iter, St->rr, St->atol);
+          if (code) St->done = code;
+        }
+      }
     });
   }
 };
 
 // KB: z = L t + ε r ; ρ_k = r·z, ‖r_k‖² -> the system's last arriver keeps ρ_k (EpiZ::fin) and runs
 // scipy's top-of-loop test on ‖r_k‖ (ProCheck / k_update_p_g): every tile of the system has
-// already passed this launch's prologue, so setting `done` here is seen first by UP
-template <typename T>
+// already passed this launch's prologue, so setting `done` here is seen first by UP.
+// SCALED: z = L t + (ε r)/d, EpiZ<T, true>'s expression
+template <typename T, bool SCALED = false>
 struct EpiZB {
   static constexpr int NDOT = 2;
   static constexpr bool CUSTOM_FINISH = true;
@@ -150,10 +197,13 @@ struct EpiZB {
   double* partials;
   unsigned* tickets;
   BatchMap m;
+  const T* d = nullptr;
   __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
     const T ri = gld(r + i);
-    const T zi = s + eps * ri;
+    T zi;
+    if constexpr (SCALED) zi = s + (eps * ri) / gld(d + i);
+    else zi = s + eps * ri;
     gst(z + i, zi);
     dd_fma(dots[0], double(ri), double(zi));
     dd_fma(dots[1], double(ri), double(ri));
@@ -239,13 +289,65 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r(BatchMap m, const P
   r[i] = ri - T(St->alpha) * qi;
 }
 
+// The elementwise tile's own dots of the three-launch UR: r_{k+1} = r_k - α q stored, Jacobi's
+// z = r/d stored, dots[0] = ‖r_{k+1}‖², dots[ND - 1] = ρ_{k+1} = r·z (k_update_r's expressions)
+template <typename T, int PRE>
+__device__ __forceinline__ void update_r_row(int64_t i, T ri, T qi, T alpha, T* __restrict__ r,
+                                             const T* __restrict__ d, T* __restrict__ z,
+                                             DD (&dots)[PRE == LSPCG_PRECOND_DIAGONAL ? 2 : 1]) {
+  const T rn = ri - alpha * qi;
+  r[i] = rn;
+  dd_fma(dots[0], double(rn), double(rn));
+  if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
+    const T zi = rn / d[i];
+    z[i] = zi;
+    dd_fma(dots[1], double(rn), double(zi));
+  }
+}
+
+// UR of the three-launch schedule (no preconditioner / Jacobi), last-arriver mode: the update, then
+// the per-system reduction over the system's ELEMENTWISE tiles (m.bs per SpMV tile: tickets `tk0`
+// / `tickets` and `partials` are this launch's own, sized for it).  KC's last arriver has already
+// counted the iteration (EpiQB), so the system's last arriver here keeps ‖r_{k+1}‖² and ρ_{k+1}
+// (k_update_r's fin) and runs iteration k+1's top-of-loop test: every tile of the system has read
+// `done` and α by then, and UP is the first launch to see the new `done`.
+template <typename T, int PRE>
+__global__ void __launch_bounds__(kThreads) k_batch_update_r_dots(BatchMap m, PcgState* S, const T* __restrict__ q,
+                                                                  T* __restrict__ r, const T* __restrict__ d,
+                                                                  T* __restrict__ z, double* partials,
+                                                                  unsigned* tickets, const int32_t* __restrict__ tk0) {
+  constexpr int ND = PRE == LSPCG_PRECOND_DIAGONAL ? 2 : 1;
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  const T ri = r[i], qi = q[i];
+  const int sys = m.etile_sys[blockIdx.x];
+  PcgState* Sb = S;
+  if (Sb[sys].done) return;  // workgroup-uniform
+  DD dots[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) dots[j] = dd_zero();
+  update_r_row<T, PRE>(i, ri, qi, T(Sb[sys].alpha), r, d, z, dots);
+  const int t0 = m.tile0[sys] * m.bs, nt = (m.tile0[sys + 1] - m.tile0[sys]) * m.bs;
+  sys_reduce_tiles<ND>(dots, partials, tickets + size_t(kTicketStride) * tk0[sys], sys, t0, nt,
+                       [Sb](int s, const double* v) {
+                         PcgState* St = Sb + s;
+                         const double rr2 = round_to<T>(v[0]);
+                         St->rr = rr2;
+                         St->rho_prev = St->rho;
+                         St->rho = PRE == LSPCG_PRECOND_DIAGONAL ? round_to<T>(v[ND - 1]) : rr2;
+                         const int64_t it = St->iter;  // k + 1 (EpiQB)
+                         if (St->hist) St->hist[it] = double(tsqrt<T>(T(rr2)));
+                         const int code = loop_test<T>(it, St->max_iter, rr2, St->atol);
+                         if (code) St->done = code;
+                       });
+}
+
 // ---- consumer-sum mode (windows whose systems have <= 128 tiles each): KB / KC only store
 // per-tile partials (grid_partial_groups, gsz = 1: no tickets) and every UP / UR workgroup sums its
 // system's tile partials itself (group_sum_dd, one wave for <= 256) ------------------------------
-// init: r_0 = b - A x0 ; per-tile partials of ‖r_0‖², ‖b‖²
-template <typename T>
+// init: r_0 = b - A x0 ; per-tile partials of ‖r_0‖², ‖b‖² (PRE = DIAGONAL: + z_0 = r_0/d and ρ_0)
+template <typename T, int PRE = LSPCG_PRECOND_EXT_SPAI>
 struct EpiResidTile {
-  static constexpr int NDOT = 2;
+  static constexpr int NDOT = PRE == LSPCG_PRECOND_DIAGONAL ? 3 : 2;
   static constexpr bool GROUPS = true;
   T* r;
   const T* b;
@@ -253,6 +355,8 @@ struct EpiResidTile {
   unsigned* ticket;
   double* group_out;
   int gsz;
+  const T* d = nullptr;
+  T* z = nullptr;
   __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
     const T bi = gld(b + i);
@@ -260,34 +364,35 @@ struct EpiResidTile {
     gst(r + i, ri);
     dd_fma(dots[0], double(ri), double(ri));
     dd_fma(dots[1], double(bi), double(bi));
+    if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
+      const T zi = ri / gld(d + i);
+      gst(z + i, zi);
+      dd_fma(dots[2], double(ri), double(zi));
+    }
   }
   __device__ __forceinline__ void fin(const double*) const {}
 };
 
 // one workgroup per system: the init state from the system's tile partials (EpiResid::fin)
-template <typename T>
+template <typename T, int PRE = LSPCG_PRECOND_EXT_SPAI>
 __global__ void __launch_bounds__(kThreads) k_batch_init(PcgState* S, const int32_t* __restrict__ tile0,
                                                          const double* __restrict__ gi) {
+  constexpr int ND = PRE == LSPCG_PRECOND_DIAGONAL ? 3 : 2;
   const int sys = blockIdx.x;
   const int t0 = tile0[sys], t1 = tile0[sys + 1];
-  double v[2];
-  group_sum_dd<2>(gi + size_t(t0) * 4, t1 - t0, v);
+  double v[ND];
+  group_sum_dd<ND>(gi + size_t(t0) * 2 * ND, t1 - t0, v);
   if (threadIdx.x) return;
-  PcgState* St = S + sys;
-  St->rr = round_to<T>(v[0]);
-  St->bb = round_to<T>(v[1]);
-  const double bn = double(tsqrt<T>(T(St->bb)));
-  St->atol = fmax(0.0, St->rtol * bn);
-  St->rho = St->rr;
-  St->alpha = 0.0;
-  St->iter = 0;
-  St->done = (bn == 0.0) ? 1 : 0;
-  if (St->hist) St->hist[0] = double(tsqrt<T>(T(St->rr)));
+  init_state<T, PRE>(S + sys, v);
 }
 
 // consumer-sum mode: UP of the split schedule (k_update_p_g) for the tile's system, summing the
 // system's tile partials itself
-template <typename T>
+// CG (three-launch schedule): gz holds UR's per-ELEMENTWISE-tile partials (bs per SpMV tile) of
+// ρ_k, ‖r_k‖² for k > 0 (iteration 0 takes both from the init state), z is r without a
+// preconditioner, and the system's first workgroup leaves ρ_k in the state for UR (rho_k, as
+// k_update_p_g), which overwrites gz
+template <typename T, bool CG = false>
 __global__ void __launch_bounds__(kThreads) k_batch_update_p_sums(BatchMap m, PcgState* S, const double* __restrict__ gz,
                                                              const T* __restrict__ z, T* __restrict__ p,
                                                              T* __restrict__ x) {
@@ -300,10 +405,11 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_p_sums(BatchMap m, Pc
   const T zi = z[i], pi = p[i], xi = x[i];
   const int t0 = m.tile0[sys], t1 = m.tile0[sys + 1];
   const int64_t k = St->iter;
+  const int per = CG ? m.bs : 1;
   double v[2];
-  group_sum_dd<2>(gz + size_t(t0) * 4, t1 - t0, v);
+  group_sum_dd<2>(gz + size_t(t0) * per * 4, (t1 - t0) * per, v);
   if (done) return;
-  const double rho = round_to<T>(v[0]);
+  const double rho = (!CG || k > 0) ? round_to<T>(v[0]) : St->rho;
   const double rr = k > 0 ? round_to<T>(v[1]) : St->rr;
   int code = 0;
   if (k >= St->max_iter) {
@@ -319,6 +425,7 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_p_sums(BatchMap m, Pc
       if (St->hist) St->hist[k] = double(tsqrt<T>(T(rr)));
     }
     if (code) St->done = code;
+    else if constexpr (CG) St->rho_k = rho;
   }
   if (code) return;
   const bool first = k == 0;
@@ -355,6 +462,59 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r_sums(BatchMap m, Pc
   r[i] = ri - alpha * qi;
 }
 
+// consumer-sum mode: UR of the three-launch schedule (k_update_r_gd) for the tile's system:
+// α_k = ρ_k/π_k from the state's ρ_k (UP) and KC's tile partials, the update, and this elementwise
+// tile's partials of ρ_{k+1}, ‖r_{k+1}‖² for the next UP (plain stores: read after the kernel boundary)
+template <typename T, int PRE>
+__global__ void __launch_bounds__(kThreads) k_batch_update_r_sums_cg(BatchMap m, PcgState* S,
+                                                                     const double* __restrict__ gq,
+                                                                     const T* __restrict__ q, T* __restrict__ r,
+                                                                     const T* __restrict__ d, T* __restrict__ z,
+                                                                     double* __restrict__ gz) {
+  constexpr int ND = PRE == LSPCG_PRECOND_DIAGONAL ? 2 : 1;
+  __shared__ DD lds[16 * ND];
+  const int sys = m.etile_sys[blockIdx.x];
+  PcgState* St = S + sys;
+  if (St->done) return;  // written by UP only: uniform over this launch
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  const T ri = r[i], qi = q[i];
+  const int t0 = m.tile0[sys], t1 = m.tile0[sys + 1];
+  const double rho = St->rho_k;
+  double vq[1];
+  group_sum_dd<1>(gq + size_t(t0) * 2, t1 - t0, vq);
+  const double pq = round_to<T>(vq[0]);
+  const T alpha = T(rho) / T(pq);
+  if (int64_t(blockIdx.x) == int64_t(t0) * m.bs && threadIdx.x == 0) {
+    St->rho_prev = St->rho;
+    St->rho = rho;
+    St->pq = pq;
+    St->alpha = double(alpha);
+    St->iter = St->iter + 1;
+  }
+  DD dots[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) dots[j] = dd_zero();
+  update_r_row<T, PRE>(i, ri, qi, alpha, r, d, z, dots);
+  block_reduce_dd<ND>(dots, lds);
+  if (threadIdx.x == 0) {
+    double* out = gz + size_t(blockIdx.x) * 4;  // [ρ | ‖r‖²], DD each
+    out[0] = dots[ND - 1].s;
+    out[1] = dots[ND - 1].c;
+    out[2] = dots[0].s;
+    out[3] = dots[0].c;
+  }
+}
+
+// padding rows of the block-diagonal system get d = 1 (diag(A) is 0 there): the divisions by d of
+// the diagonal and scaled kinds then keep them exactly 0
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_batch_pad_d(BatchMap m, const int32_t* __restrict__ boff,
+                                                          const int32_t* __restrict__ bn, T* __restrict__ d) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  const int sys = m.etile_sys[blockIdx.x];
+  if (i >= int64_t(boff[sys]) + bn[sys]) d[i] = T(1);
+}
+
 template <typename T>
 __global__ void __launch_bounds__(kThreads) k_batch_x_fixup(BatchMap m, const PcgState* S, const T* __restrict__ p,
                                                             T* __restrict__ x) {
@@ -382,6 +542,7 @@ struct lspcg_batch {
   int nsys = 0;
   int bs = 1;
   int dtype = LSPCG_F64;
+  int precond = LSPCG_PRECOND_EXT_SPAI;  // none / diagonal: the three-launch iteration
   lspcg_mat* Acat = nullptr;
   lspcg_mat* Lcat = nullptr;
   lspcg_solver* s = nullptr;  // solver of the block-diagonal system: views, vectors, stream
@@ -390,14 +551,19 @@ struct lspcg_batch {
   int32_t* etile_sys = nullptr;
   int32_t* tile0 = nullptr;
   int32_t* tk0 = nullptr;
-  double* partials = nullptr;  // per-tile dot partials (<= 2 dots, DD each)
+  double* partials = nullptr;  // per-tile dot partials of the reducing launch in flight (<= 3 dots, DD each;
+                               // SpMV row tiles, or elementwise tiles in the three-launch UR)
   unsigned* tickets = nullptr;  // per system: top line + one line per kTicketGroup tiles (batch_sys_reduce)
+  int32_t* etk0 = nullptr;      // three-launch UR: first ticket line of each system in etickets, which
+  unsigned* etickets = nullptr;  // has one line per kTicketGroup ELEMENTWISE tiles (bs per SpMV tile)
   bool sums = false;            // consumer-sum reductions (every system <= 128 tiles; LSPCG_BATCH_REDUCE)
   bool small = false;           // every system fits the one-workgroup solve: one launch, one workgroup per system
   int64_t max_n = 0;
   int32_t* boff = nullptr;      // [nsys] scalar row offset / size of each system (small mode)
   int32_t* bn = nullptr;
-  double* gsum = nullptr;       // consumer-sum partials: init (2 dots) | KB (2 dots) | KC (1 dot), per tile
+  double* gsum = nullptr;       // consumer-sum partials: init (<= 3 dots) | gz | gq, per tile
+  double* gz = nullptr;         // ... ρ, ‖r‖²: KB's per SpMV tile, or the three-launch UR's per elementwise tile
+  double* gq = nullptr;         // ... π: KC's per SpMV tile
   int64_t ntiles = 0;
   PcgState* S = nullptr;
   PcgState* hS = nullptr;  // pinned: 2 poll slots x nsys
@@ -428,25 +594,67 @@ static int launch_it_tiles(lspcg_solver* s, int w, const T* x, Pro pro, Epi epi,
 template <typename T>
 static int enqueue_batch_init(lspcg_batch* bt, hipStream_t st) {
   lspcg_solver* s = bt->s;
+  T* r = static_cast<T*>(s->r);
+  const T* b = static_cast<const T*>(s->b);
+  const T* x = static_cast<const T*>(s->x);
+  const T* d = static_cast<const T*>(s->d);
+  T* z = static_cast<T*>(s->z);
+  // PRE: EXT_SPAI stands for both ext_spai kinds (their init has no preconditioner part)
+  auto go = [&](auto pre) -> int {
+    constexpr int PRE = decltype(pre)::value;
+    if (bt->sums) {
+      int rc = launch_it_tiles<T>(s, 0, x, ProNone{}, EpiResidTile<T, PRE>{r, b, nullptr, nullptr, bt->gsum, 1, d, z},
+                                  st);
+      if (rc) return rc;
+      hipLaunchKernelGGL((k_batch_init<T, PRE>), dim3(bt->nsys), dim3(kThreads), 0, st, bt->S,
+                         static_cast<const int32_t*>(bt->tile0), static_cast<const double*>(bt->gsum));
+      LSPCG_HIP(hipGetLastError());
+      return LSPCG_OK;
+    }
+    return launch_it_tiles<T>(s, 0, x, ProNone{},
+                              EpiResidB<T, PRE>{r, b, bt->S, bt->partials, bt->tickets, batch_map(bt), d, z}, st);
+  };
+  if (bt->precond == LSPCG_PRECOND_NONE) return go(std::integral_constant<int, LSPCG_PRECOND_NONE>{});
+  if (bt->precond == LSPCG_PRECOND_DIAGONAL) return go(std::integral_constant<int, LSPCG_PRECOND_DIAGONAL>{});
+  return go(std::integral_constant<int, LSPCG_PRECOND_EXT_SPAI>{});
+}
+
+// the three-launch iteration of the kinds without KA / KB (no preconditioner, Jacobi): UP, KC, UR
+template <typename T, int PRE>
+static int enqueue_batch_iteration_cg(lspcg_batch* bt, hipStream_t st) {
+  lspcg_solver* s = bt->s;
+  T* x = static_cast<T*>(s->x);
+  T* r = static_cast<T*>(s->r);
+  T* z = static_cast<T*>(s->z);
+  T* p = static_cast<T*>(s->p);
+  T* q = static_cast<T*>(s->q);
+  const T* d = static_cast<const T*>(s->d);
+  const T* zp = PRE == LSPCG_PRECOND_NONE ? r : z;  // z = r without a preconditioner
+  const BatchMap m = batch_map(bt);
+  const ProTile pro{bt->S, m};
+  const dim3 eg(unsigned(bt->ntot / kThreads));
+  int rc = LSPCG_OK;
   if (bt->sums) {
-    int rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(s->x), ProNone{},
-                                EpiResidTile<T>{static_cast<T*>(s->r), static_cast<const T*>(s->b), nullptr, nullptr,
-                                                bt->gsum, 1},
-                                st);
+    hipLaunchKernelGGL((k_batch_update_p_sums<T, true>), eg, dim3(kThreads), 0, st, m, bt->S,
+                       static_cast<const double*>(bt->gz), zp, p, x);
+    rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(p), pro, EpiQG<T>{q, p, nullptr, nullptr, bt->gq, 1}, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_batch_init<T>, dim3(bt->nsys), dim3(kThreads), 0, st, bt->S,
-                       static_cast<const int32_t*>(bt->tile0), static_cast<const double*>(bt->gsum));
+    hipLaunchKernelGGL((k_batch_update_r_sums_cg<T, PRE>), eg, dim3(kThreads), 0, st, m, bt->S,
+                       static_cast<const double*>(bt->gq), static_cast<const T*>(q), r, d, z, bt->gz);
     LSPCG_HIP(hipGetLastError());
     return LSPCG_OK;
   }
-  return launch_it_tiles<T>(s, 0, static_cast<const T*>(s->x), ProNone{},
-                            EpiResidB<T>{static_cast<T*>(s->r), static_cast<const T*>(s->b), bt->S, bt->partials,
-                                         bt->tickets, batch_map(bt)},
-                            st);
+  hipLaunchKernelGGL(k_batch_update_p<T>, eg, dim3(kThreads), 0, st, m, static_cast<const PcgState*>(bt->S), zp, p, x);
+  rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(p), pro, EpiQB<T>{q, p, bt->S, bt->partials, bt->tickets, m}, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL((k_batch_update_r_dots<T, PRE>), eg, dim3(kThreads), 0, st, m, bt->S, static_cast<const T*>(q), r,
+                     d, z, bt->partials, bt->etickets, static_cast<const int32_t*>(bt->etk0));
+  LSPCG_HIP(hipGetLastError());
+  return LSPCG_OK;
 }
 
-template <typename T>
-static int enqueue_batch_iteration(lspcg_batch* bt, hipStream_t st) {
+template <typename T, bool SC>
+static int enqueue_batch_iteration_spai(lspcg_batch* bt, hipStream_t st) {
   lspcg_solver* s = bt->s;
   T* x = static_cast<T*>(s->x);
   T* r = static_cast<T*>(s->r);
@@ -457,13 +665,14 @@ static int enqueue_batch_iteration(lspcg_batch* bt, hipStream_t st) {
   const BatchMap m = batch_map(bt);
   const ProTile pro{bt->S, m};
   const dim3 eg(unsigned(bt->ntot / kThreads));
-  int rc = launch_it_tiles<T>(s, 2, static_cast<const T*>(r), pro, EpiT<T, false>{t, nullptr}, st);
+  const T* d = SC ? static_cast<const T*>(s->d) : nullptr;
+  int rc = launch_it_tiles<T>(s, 2, static_cast<const T*>(r), pro, EpiT<T, SC>{t, d}, st);
   if (rc) return rc;
   if (bt->sums) {
-    double* gz = bt->gsum + 4 * bt->ntiles;
-    double* gq = bt->gsum + 8 * bt->ntiles;
+    double* gz = bt->gz;
+    double* gq = bt->gq;
     rc = launch_it_tiles<T>(s, 1, static_cast<const T*>(t), pro,
-                            EpiZG<T, false>{z, r, nullptr, T(s->eps), nullptr, nullptr, gz, 1}, st);
+                            EpiZG<T, SC>{z, r, d, T(s->eps), nullptr, nullptr, gz, 1}, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_batch_update_p_sums<T>, eg, dim3(kThreads), 0, st, m, bt->S, static_cast<const double*>(gz),
                        static_cast<const T*>(z), p, x);
@@ -475,7 +684,7 @@ static int enqueue_batch_iteration(lspcg_batch* bt, hipStream_t st) {
     return LSPCG_OK;
   }
   rc = launch_it_tiles<T>(s, 1, static_cast<const T*>(t), pro,
-                          EpiZB<T>{z, r, T(s->eps), bt->S, bt->partials, bt->tickets, m}, st);
+                          EpiZB<T, SC>{z, r, T(s->eps), bt->S, bt->partials, bt->tickets, m, d}, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_batch_update_p<T>, eg, dim3(kThreads), 0, st, m, static_cast<const PcgState*>(bt->S),
                      static_cast<const T*>(z), p, x);
@@ -488,12 +697,25 @@ static int enqueue_batch_iteration(lspcg_batch* bt, hipStream_t st) {
   return LSPCG_OK;
 }
 
+template <typename T>
+static int enqueue_batch_iteration(lspcg_batch* bt, hipStream_t st) {
+  switch (bt->precond) {
+    case LSPCG_PRECOND_NONE: return enqueue_batch_iteration_cg<T, LSPCG_PRECOND_NONE>(bt, st);
+    case LSPCG_PRECOND_DIAGONAL: return enqueue_batch_iteration_cg<T, LSPCG_PRECOND_DIAGONAL>(bt, st);
+    case LSPCG_PRECOND_EXT_SPAI_SCALED: return enqueue_batch_iteration_spai<T, true>(bt, st);
+    default: return enqueue_batch_iteration_spai<T, false>(bt, st);
+  }
+}
+
 // every system of the window in its own workgroup (k_pcg_small in batch mode): the whole loop in
 // one launch; rows per thread / threads from the window's largest system (launch_small's rule)
 template <typename T>
 static int launch_batch_small(lspcg_batch* bt, hipStream_t st) {
   lspcg_solver* s = bt->s;
-  const CsrView A = csr_view(s, 0, s->Av), L = csr_view(s, 1, s->Lv), LT = csr_view(s, 2, s->LTv);
+  const bool spai = bt->precond == LSPCG_PRECOND_EXT_SPAI || bt->precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
+  const CsrView A = csr_view(s, 0, s->Av);
+  const CsrView L = spai ? csr_view(s, 1, s->Lv) : CsrView{};
+  const CsrView LT = spai ? csr_view(s, 2, s->LTv) : CsrView{};
   auto* x = static_cast<T*>(s->x);
   auto* r = static_cast<T*>(s->r);
   auto* p = static_cast<T*>(s->p);
@@ -504,8 +726,25 @@ static int launch_batch_small(lspcg_batch* bt, hipStream_t st) {
   auto go = [&](auto rows, auto threads) {
     constexpr int R = decltype(rows)::value;
     constexpr int TH = decltype(threads)::value;
-    hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_EXT_SPAI, R, TH>), g, dim3(TH), lds, st, int32_t(n), bt->S, A, L,
-                       LT, d, x, r, p, static_cast<const int32_t*>(bt->boff), static_cast<const int32_t*>(bt->bn));
+    const int32_t* boff = bt->boff;
+    const int32_t* bn = bt->bn;
+    switch (bt->precond) {  // d: of the block-diagonal system, 1 on padding rows (which no workgroup owns)
+      case LSPCG_PRECOND_NONE:
+        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_NONE, R, TH>), g, dim3(TH), lds, st, int32_t(n), bt->S, A, L,
+                           LT, d, x, r, p, boff, bn);
+        break;
+      case LSPCG_PRECOND_DIAGONAL:
+        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_DIAGONAL, R, TH>), g, dim3(TH), lds, st, int32_t(n), bt->S, A,
+                           L, LT, d, x, r, p, boff, bn);
+        break;
+      case LSPCG_PRECOND_EXT_SPAI_SCALED:
+        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_EXT_SPAI_SCALED, R, TH>), g, dim3(TH), lds, st, int32_t(n),
+                           bt->S, A, L, LT, d, x, r, p, boff, bn);
+        break;
+      default:
+        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_EXT_SPAI, R, TH>), g, dim3(TH), lds, st, int32_t(n), bt->S, A,
+                           L, LT, d, x, r, p, boff, bn);
+    }
   };
   dispatch_small(n, go);
   LSPCG_HIP(hipGetLastError());
@@ -554,7 +793,7 @@ int lspcg_batch_destroy(lspcg_batch* bt) {
   if (bt->s) lspcg_solver_destroy(bt->s);
   if (bt->Acat) lspcg_mat_destroy(bt->Acat);
   if (bt->Lcat) lspcg_mat_destroy(bt->Lcat);
-  for (void* v : {(void*)bt->boff, (void*)bt->bn, (void*)bt->etile_sys, (void*)bt->tile0, (void*)bt->tk0, (void*)bt->gsum, (void*)bt->partials, (void*)bt->tickets, (void*)bt->S,
+  for (void* v : {(void*)bt->boff, (void*)bt->bn, (void*)bt->etile_sys, (void*)bt->tile0, (void*)bt->tk0, (void*)bt->etk0, (void*)bt->etickets, (void*)bt->gsum, (void*)bt->partials, (void*)bt->tickets, (void*)bt->S,
                   (void*)bt->dhist})
     (void)hipFree(v);
   (void)hipHostFree(bt->hS);
@@ -564,19 +803,34 @@ int lspcg_batch_destroy(lspcg_batch* bt) {
 
 int lspcg_batch_create(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, const lspcg_mat* const* L,
                        double epsilon, lspcg_batch** out) {
-  LSPCG_CHECK(ctx && A && L && out && nsys >= 1, LSPCG_ERR_ARG, "batch_create: NULL argument or nsys < 1");
+  return lspcg_batch_create_precond(ctx, nsys, A, L, LSPCG_PRECOND_EXT_SPAI, epsilon, out);
+}
+
+int lspcg_batch_create_precond(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, const lspcg_mat* const* L,
+                               int precond, double epsilon, lspcg_batch** out) {
+  LSPCG_CHECK(ctx && A && out && nsys >= 1, LSPCG_ERR_ARG, "batch_create: NULL argument or nsys < 1");
+  LSPCG_CHECK(precond != LSPCG_PRECOND_IC, LSPCG_ERR_UNSUPPORTED,
+              "batch_create: IC's triangular solves do not run in lockstep: solve one by one");
+  LSPCG_CHECK(precond >= LSPCG_PRECOND_NONE && precond <= LSPCG_PRECOND_EXT_SPAI_SCALED, LSPCG_ERR_ARG,
+              "batch_create: unknown preconditioner " + std::to_string(precond));
+  const bool spai = precond == LSPCG_PRECOND_EXT_SPAI || precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
+  const bool needs_d = precond == LSPCG_PRECOND_DIAGONAL || precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
+  LSPCG_CHECK(spai ? L != nullptr : L == nullptr, LSPCG_ERR_ARG,
+              spai ? "batch_create: the ext_spai kinds need L" : "batch_create: L must be NULL for none / diagonal");
+  if (!spai) epsilon = 0.0;
   for (int k = 0; k < nsys; ++k) {
-    LSPCG_CHECK(A[k] && L[k], LSPCG_ERR_ARG, "batch_create: NULL matrix " + std::to_string(k));
-    LSPCG_CHECK(A[k]->dtype == A[0]->dtype && L[k]->dtype == A[0]->dtype, LSPCG_ERR_ARG,
+    LSPCG_CHECK(A[k] && (!spai || L[k]), LSPCG_ERR_ARG, "batch_create: NULL matrix " + std::to_string(k));
+    LSPCG_CHECK(A[k]->dtype == A[0]->dtype && (!spai || L[k]->dtype == A[0]->dtype), LSPCG_ERR_ARG,
                 "batch_create: every A and L must have one dtype");
-    LSPCG_CHECK(A[k]->block_size == A[0]->block_size && L[k]->block_size == A[0]->block_size, LSPCG_ERR_ARG,
+    LSPCG_CHECK(A[k]->block_size == A[0]->block_size && (!spai || L[k]->block_size == A[0]->block_size), LSPCG_ERR_ARG,
                 "batch_create: every A and L must have one block size");
-    LSPCG_CHECK(L[k]->n == A[k]->n && A[k]->n >= 1, LSPCG_ERR_ARG,
+    LSPCG_CHECK((!spai || L[k]->n == A[k]->n) && A[k]->n >= 1, LSPCG_ERR_ARG,
                 "batch_create: system " + std::to_string(k) + ": L and A differ in size or are empty");
   }
   LSPCG_HIP(hipSetDevice(ctx->device));
   std::unique_ptr<lspcg_batch, int (*)(lspcg_batch*)> bt(new lspcg_batch(), lspcg_batch_destroy);
   bt->ctx = ctx;
+  bt->precond = precond;
   bt->nsys = nsys;
   bt->bs = A[0]->block_size;
   bt->dtype = A[0]->dtype;
@@ -590,7 +844,8 @@ int lspcg_batch_create(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, cons
   }
   bt->ntot = brow[nsys] * bt->bs;
   if (int rc = cat_matrices(ctx, nsys, A, brow, &bt->Acat)) return rc;
-  if (int rc = cat_matrices(ctx, nsys, L, brow, &bt->Lcat)) return rc;
+  if (spai)
+    if (int rc = cat_matrices(ctx, nsys, L, brow, &bt->Lcat)) return rc;
   // one workgroup per system when every system fits the one-workgroup solve (scalar views; its
   // row and LDS bounds, small_path); LSPCG_BATCH_SMALL=0 keeps the lockstep phases.  Decided before
   // the views are built: that mode reads 4-entry-group SELL copies, not SELL-DIA
@@ -603,9 +858,10 @@ int lspcg_batch_create(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, cons
     bt->small = !(e && e[0] == '0') && bt->bs == 1 && bt->max_n <= std::min<int64_t>(row_cap, small_n) &&
                 3 * bt->max_n * int64_t(esize(bt->dtype)) <= kSmallLds;
   }
-  if (int rc = solver_create(ctx, bt->Acat, LSPCG_PRECOND_EXT_SPAI, !bt->small, false, &bt->s)) return rc;
-  if (int rc = lspcg_solver_set_spai(bt->s, bt->Lcat, epsilon, nullptr)) return rc;
-  LSPCG_CHECK(bt->s->sp[0] && bt->s->sp[1] && bt->s->sp[2], LSPCG_ERR_UNSUPPORTED,
+  if (int rc = solver_create(ctx, bt->Acat, precond, !bt->small, false, &bt->s)) return rc;
+  if (spai)
+    if (int rc = lspcg_solver_set_spai(bt->s, bt->Lcat, epsilon, nullptr)) return rc;
+  LSPCG_CHECK(bt->s->sp[0] && (!spai || (bt->s->sp[1] && bt->s->sp[2])), LSPCG_ERR_UNSUPPORTED,
               "batch_create: no SELL view of the block-diagonal system (irregular rows): solve one by one");
   // tile maps
   const int64_t ntiles = brow[nsys] / kSellWG;
@@ -628,7 +884,21 @@ int lspcg_batch_create(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, cons
   LSPCG_HIP(hipMalloc(&bt->tile0, sizeof(int32_t) * t0.size()));
   LSPCG_HIP(hipMemcpy(bt->etile_sys, esys.data(), sizeof(int32_t) * esys.size(), hipMemcpyHostToDevice));
   LSPCG_HIP(hipMemcpy(bt->tile0, t0.data(), sizeof(int32_t) * t0.size(), hipMemcpyHostToDevice));
-  LSPCG_HIP(hipMalloc(&bt->partials, sizeof(double) * 4 * ntiles));
+  // partials: <= 3 dots per SpMV tile (Jacobi's init), <= 2 per elementwise tile (three-launch UR)
+  const int64_t netiles = bt->ntot / kThreads;  // = ntiles * bs
+  LSPCG_HIP(hipMalloc(&bt->partials, sizeof(double) * std::max<int64_t>(6 * ntiles, 4 * netiles)));
+  if (!spai) {  // the three-launch UR's tickets: per system, top line + one line per kTicketGroup elementwise tiles
+    std::vector<int32_t> etk(nsys);
+    int64_t elines = 0;
+    for (int k = 0; k < nsys; ++k) {
+      etk[k] = int32_t(elines);
+      elines += 1 + (int64_t(t0[k + 1] - t0[k]) * bt->bs + kTicketGroup - 1) / kTicketGroup;
+    }
+    LSPCG_HIP(hipMalloc(&bt->etk0, sizeof(int32_t) * nsys));
+    LSPCG_HIP(hipMemcpy(bt->etk0, etk.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
+    LSPCG_HIP(hipMalloc(&bt->etickets, sizeof(unsigned) * kTicketStride * elines));
+    LSPCG_HIP(hipMemset(bt->etickets, 0, sizeof(unsigned) * kTicketStride * elines));
+  }
   // reductions: consumer sums when every system has <= 128 tiles (C5 heat, <= 117 tiles: 25.6 vs
   // 26.8 us per lockstep iteration), else per-system last arrivers (8 x Poisson 256^2, 256 tiles:
   // 47.1 vs 49.9); LSPCG_BATCH_REDUCE=0 / 1 forces either
@@ -637,8 +907,16 @@ int lspcg_batch_create(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, cons
   bt->sums = max_nt <= 128;
   if (const char* e = std::getenv("LSPCG_BATCH_REDUCE")) bt->sums = e[0] == '1';
   bt->ntiles = ntiles;
-  LSPCG_HIP(hipMalloc(&bt->gsum, sizeof(double) * 10 * ntiles));
-  if (bt->small) {
+  // consumer-sum partials: init (<= 3 dots per SpMV tile) | gz (2 dots per SpMV tile from KB, or per
+  // elementwise tile from the three-launch UR) | gq (1 dot per SpMV tile)
+  {
+    const int64_t ni = spai ? 4 * ntiles : 6 * ntiles, nz = spai ? 4 * ntiles : 4 * netiles;
+    LSPCG_HIP(hipMalloc(&bt->gsum, sizeof(double) * (ni + nz + 2 * ntiles)));
+    LSPCG_HIP(hipMemset(bt->gsum, 0, sizeof(double) * (ni + nz + 2 * ntiles)));
+    bt->gz = bt->gsum + ni;
+    bt->gq = bt->gz + nz;
+  }
+  if (bt->small || needs_d) {
     std::vector<int32_t> ho(nsys), hn(nsys);
     for (int k = 0; k < nsys; ++k) {
       ho[k] = int32_t(bt->off[k]);
@@ -648,6 +926,19 @@ int lspcg_batch_create(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* A, cons
     LSPCG_HIP(hipMalloc(&bt->bn, sizeof(int32_t) * nsys));
     LSPCG_HIP(hipMemcpy(bt->boff, ho.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
     LSPCG_HIP(hipMemcpy(bt->bn, hn.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
+  }
+  if (needs_d) {  // d = diag of the block-diagonal system (solver_create / set_spai), 1 on padding rows
+    const dim3 eg{unsigned(netiles)};
+    if (bt->dtype == LSPCG_F64)
+      hipLaunchKernelGGL(k_batch_pad_d<double>, eg, dim3(kThreads), 0, ctx->stream, batch_map(bt.get()),
+                         static_cast<const int32_t*>(bt->boff), static_cast<const int32_t*>(bt->bn),
+                         static_cast<double*>(bt->s->d));
+    else
+      hipLaunchKernelGGL(k_batch_pad_d<float>, eg, dim3(kThreads), 0, ctx->stream, batch_map(bt.get()),
+                         static_cast<const int32_t*>(bt->boff), static_cast<const int32_t*>(bt->bn),
+                         static_cast<float*>(bt->s->d));
+    LSPCG_HIP(hipGetLastError());
+    LSPCG_HIP(hipStreamSynchronize(ctx->stream));
   }
   LSPCG_HIP(hipMalloc(&bt->tickets, sizeof(unsigned) * kTicketStride * lines));
   LSPCG_HIP(hipMemset(bt->tickets, 0, sizeof(unsigned) * kTicketStride * lines));

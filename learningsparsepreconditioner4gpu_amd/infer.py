@@ -37,7 +37,8 @@ from . import problems as P
 from .data import GraphSample
 from .data import make_sample as _make_sample
 from .distributed import SolveRecord, run_sharded, run_sharded_batched, run_sharded_concurrent
-from .validate import get_cg_iter_time, get_pcg_iter_time, get_pcg_iter_time_batch, get_pcg_scaled_iter_time
+from .validate import (get_cg_iter_time, get_cg_iter_time_batch, get_pcg_iter_time, get_pcg_iter_time_batch,
+                       get_pcg_scaled_iter_time, get_pcg_scaled_iter_time_batch)
 from .workspace import ScaledInferenceWorkspace, SimpleInferenceWorkspace
 
 
@@ -189,15 +190,18 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
     """The ``Neural+CUDA`` row of infer.py:278-331 (GNN -> L, A; ext_spai PCG).  ``concurrency``
     > 1 keeps that many solves of this rank in flight at once (run_sharded_concurrent): the same
     iterates and counts, a higher batch throughput on the reference's mid-size systems.  ``batch``
-    > 1 (ext_spai, not the scaled variant) solves this rank's systems in lockstep windows of that
-    many (run_sharded_batched, validate.get_pcg_iter_time_batch) after ONE GNN forward over the
+    > 1 (ext_spai, or its scaled variant for a ScaledInferenceWorkspace) solves this rank's systems
+    in lockstep windows of that many (run_sharded_batched, validate.get_pcg_iter_time_batch /
+    get_pcg_scaled_iter_time_batch) after ONE GNN forward over the
     window's graphs (workspace.inference_step_batch): the same L, counts and iterates, every launch
     covering the whole window; a record's t_prec / t_solve are its shares of the window's forward
     / device solve time.  ``dot_order`` / ``dot_threads``: the loop's dot order (``"openblas"`` =
     parity mode; not with ``batch`` > 1, whose lockstep schedule has the compensated order only)."""
     if batch > 1 and dot_order != "compensated":
         raise ValueError("batch > 1 runs the compensated dot order only; use batch=1 for dot_order='openblas'")
-    pcg = get_pcg_scaled_iter_time if isinstance(ws, ScaledInferenceWorkspace) else get_pcg_iter_time
+    scaled = isinstance(ws, ScaledInferenceWorkspace)
+    pcg = get_pcg_scaled_iter_time if scaled else get_pcg_iter_time
+    pcg_batch = get_pcg_scaled_iter_time_batch if scaled else get_pcg_iter_time_batch
     dev = torch.device("cuda", torch.cuda.current_device())
     warmed = set()
 
@@ -228,8 +232,8 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
 
     def finish_batch(jobs) -> List[SolveRecord]:
         infos = [{} for _ in jobs]
-        out = get_pcg_iter_time_batch([j[1] for j in jobs], [j[3] for j in jobs], [j[2] for j in jobs], ws.epsilon,
-                                      rtol=rtol, infos=infos, repeat=repeat)
+        out = pcg_batch([j[1] for j in jobs], [j[3] for j in jobs], [j[2] for j in jobs], ws.epsilon,
+                        rtol=rtol, infos=infos, repeat=repeat)
         return [SolveRecord(index=j[0], iters=it, rel_res=info["rel_res"], t_prec=j[4], t_solve=sol, n=j[1].n,
                             nnz=j[1].nnz, converged=info["converged"]) for j, (it, _, sol), info in zip(jobs, out, infos)]
 
@@ -251,7 +255,7 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
                 for i, s, L in zip(items, ss, Ls)]
 
     weights = [float(s.edge_index.shape[1]) for s in samples]
-    if batch > 1 and not isinstance(ws, ScaledInferenceWorkspace):
+    if batch > 1:
         return run_sharded_batched(len(samples), weights, prepare, finish_batch, batch, prepare_batch=prepare_batch)
     if concurrency > 1:
         return run_sharded_concurrent(len(samples), weights, prepare, finish, concurrency)
@@ -260,11 +264,32 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
 
 def run_baseline(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, method: str, rtol: float = 1e-6,
                  repeat: int = 1, rhs: str = "mask", dot_order: str = "compensated",
-                 dot_threads: int = 1, rhs_vectors: Optional[Dict[int, np.ndarray]] = None) -> List[SolveRecord]:
+                 dot_threads: int = 1, rhs_vectors: Optional[Dict[int, np.ndarray]] = None,
+                 batch: int = 1) -> List[SolveRecord]:
     """The ``PCG-{method}-cuda`` rows (infer.py:310-321: get_cg_iter_time with method none /
     diagonal / ainv / ic on the same A and rhs).  A non-converged solve raises RuntimeError in
-    the reference (caught at :363); here its row is NaN and left out of the statistics."""
+    the reference (caught at :363); here its row is NaN and left out of the statistics.
+    ``batch`` > 1 solves this rank's systems in lockstep windows of that many for none / diagonal /
+    ainv (run_sharded_batched, validate.get_cg_iter_time_batch: the same counts and iterates, a
+    record's t_prec / t_solve its shares of the window's); ``ic`` has no lockstep form and stays one
+    solve at a time, as does the parity dot order."""
     dev = torch.device("cuda", torch.cuda.current_device())
+
+    def nan_row(i, A) -> SolveRecord:
+        return SolveRecord(index=i, iters=float("nan"), rel_res=float("nan"), t_prec=float("nan"),
+                           t_solve=float("nan"), n=A.n, nnz=A.nnz, converged=False)
+
+    def prepare(i: int):
+        s = samples[i].to(dev)
+        return i, ws.system_matrix(s), _rhs(rhs, i, s, rhs_vectors)
+
+    def finish_batch(jobs) -> List[SolveRecord]:
+        infos, errors = [{} for _ in jobs], [None for _ in jobs]
+        out = get_cg_iter_time_batch([j[1] for j in jobs], [j[2] for j in jobs], method, rtol=rtol, infos=infos,
+                                     repeat=repeat, errors=errors)
+        return [nan_row(i, A) if o is None else
+                SolveRecord(index=i, iters=o[0], rel_res=info["rel_res"], t_prec=o[1], t_solve=o[2], n=A.n, nnz=A.nnz,
+                            converged=info["converged"]) for (i, A, _), o, info in zip(jobs, out, infos)]
 
     def solve(i: int) -> SolveRecord:
         s = samples[i].to(dev)
@@ -275,12 +300,13 @@ def run_baseline(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, m
             it, prec, sol = get_cg_iter_time(A, r, rtol=rtol, repeat=repeat, method=method, device="cuda",
                                              info=info, dot_order=dot_order, dot_threads=dot_threads)
         except RuntimeError:
-            return SolveRecord(index=i, iters=float("nan"), rel_res=float("nan"), t_prec=float("nan"),
-                               t_solve=float("nan"), n=A.n, nnz=A.nnz, converged=False)
+            return nan_row(i, A)
         return SolveRecord(index=i, iters=it, rel_res=info["rel_res"], t_prec=prec, t_solve=sol, n=A.n, nnz=A.nnz,
                            converged=info["converged"])
 
     weights = [float(s.edge_index.shape[1]) for s in samples]
+    if batch > 1 and method in ("none", "diagonal", "ainv") and dot_order == "compensated":
+        return run_sharded_batched(len(samples), weights, prepare, finish_batch, batch)
     return run_sharded(len(samples), weights, solve)
 
 
@@ -376,7 +402,8 @@ def main(argv=None):
     ap.add_argument("--concurrency", type=int, default=1,
                     help="solves in flight at once per GPU (run_sharded_concurrent); 1 = the reference's sequential loop")
     ap.add_argument("--batch", type=int, default=1,
-                    help="systems per lockstep batch per GPU (run_sharded_batched); 1 = one solve at a time")
+                    help="systems per lockstep batch per GPU (run_sharded_batched) for the Neural row (either "
+                         "workspace) and the none / diagonal / ainv baselines; 1 = one solve at a time")
     ap.add_argument("--baselines", default="none,diagonal,ainv,ic",
                     help="comma list of PCG-{method}-cuda rows (infer.py:310-321); '' for none")
     ap.add_argument("--dot-order", default="compensated", choices=["compensated", "openblas"],
@@ -422,9 +449,11 @@ def main(argv=None):
     # rank 0's host rows then solve the SAME vector for a sample
     rhs_vectors = ({i: rhs_for(args.rhs, s.mask.numpy(), s, rng=np.random.default_rng(args.rhs_seed + i))
                     for i, s in enumerate(samples)} if args.rhs == "random" else None)
+    # --batch reaches every row with a lockstep form: on the heat_batch8 window each kind's batch beats
+    # its one-at-a-time sum in wall time (profiles/batch_kinds_probe.json); ic has none
     for m in [b for b in args.baselines.split(",") if b]:
         rows[f"PCG-{m}-cuda"] = run_baseline(samples, ws, m, rtol=args.rtol, repeat=args.repeat, rhs=args.rhs,
-                                             rhs_vectors=rhs_vectors, **dots)
+                                             rhs_vectors=rhs_vectors, batch=args.batch, **dots)
     key = "Neural+HIP" if args.hip_key else "Neural+CUDA"
     rows[key] = run(samples, ws, rtol=args.rtol, repeat=args.repeat, rhs=args.rhs, warmup=args.warmup,
                     concurrency=args.concurrency, batch=args.batch, rhs_vectors=rhs_vectors, **dots)

@@ -277,8 +277,11 @@ def solve_many(jobs, rtol: float = 1e-6, max_iter: int = 0, concurrency: int = 4
         return list(ex.map(lambda j: j[0].solve(j[1], j[2], rtol, max_iter), jobs))
 
 
+BATCH_KINDS = ("none", "diagonal", "ext_spai", "ext_spai_scaled", "ainv")
+
+
 class BatchedConjugateGradient:
-    """ext_spai PCG of several independent systems in lockstep (``lspcg_batch_*``).
+    """PCG of several independent systems in lockstep (``lspcg_batch_*``).
 
     The reference solves its samples one at a time (``infer.py:278-331``: one
     ``get_pcg_iter_time`` per sample, ``validate.py:89-121``).  Mid-size systems are
@@ -289,26 +292,48 @@ class BatchedConjugateGradient:
     result is what ``PreconditionedConjugateGradient`` returns for it alone.
 
     ``As[k]``, ``Ls[k]``: matrix and ext_spai factor of system k (DeviceMatrix or scipy), one
-    dtype and block size; ``epsilon``: the common ε of M⁻¹ = L Lᵀ + εI.  Raises ``LspcgError``
-    with code ``ERR_UNSUPPORTED`` when no SELL view of the batch can be built (irregular rows).
+    dtype and block size; ``epsilon``: the common ε of M⁻¹ = L Lᵀ + εI.  ``preconditioner``: the
+    kind every system is solved with, as ``PreconditionedConjugateGradient``'s -- ``"ext_spai"``
+    (default), ``"ext_spai_scaled"`` (both need ``Ls``), ``"none"`` / ``"diagonal"`` (three
+    launches per lockstep iteration; no ``Ls``) or ``"ainv"`` (L = AINV(0) of every A, built here,
+    run as ext_spai with ε = 0).  ``"ic"`` has no lockstep form.  Raises ``LspcgError`` with code
+    ``ERR_UNSUPPORTED`` when no SELL view of the batch can be built (irregular rows).
     """
 
-    def __init__(self, As, Ls, epsilon: float, dtype=np.float64, block_size: int = 1,
-                 ctx: Optional[Context] = None):
-        As, Ls = list(As), list(Ls)
-        if not As or len(As) != len(Ls):
+    def __init__(self, As, Ls=None, epsilon: float = 0.0, dtype=np.float64, block_size: int = 1,
+                 ctx: Optional[Context] = None, preconditioner: str = "ext_spai"):
+        if preconditioner not in BATCH_KINDS:
+            raise ValueError(f"preconditioner {preconditioner!r} has no lockstep batch; expected one of {BATCH_KINDS}")
+        As = list(As)
+        needs_L = preconditioner in ("ext_spai", "ext_spai_scaled")
+        if Ls is not None and not needs_L:
+            raise ValueError(f"preconditioner {preconditioner!r} takes no Ls")
+        if needs_L and Ls is None:
+            raise ValueError(f"preconditioner {preconditioner!r} needs one L per A")
+        Ls = list(Ls) if needs_L else None
+        if not As or (needs_L and len(As) != len(Ls)):
             raise ValueError("need one L per A and at least one system")
+        self.preconditioner = preconditioner
         self.ctx = ctx or (As[0].ctx if isinstance(As[0], DeviceMatrix) else Context.get())
         self.dtype = np.dtype(dtype)
         self.A = [_as_device_matrix(M, self.dtype, block_size, self.ctx) for M in As]
-        self.L = [_as_device_matrix(M, self.dtype, block_size, self.ctx) for M in Ls]
+        self.setup_time = 0.0  # device setup of the ainv factors (seconds)
+        kind = preconditioner
+        if preconditioner == "ainv":  # as the single solver: the ext_spai operator L Lᵀ + 0·I, L = lspcg_ainv0(A)
+            fac = [M.ainv0() for M in self.A]
+            self.L = [f[0] for f in fac]
+            self.setup_time = float(sum(f[1] for f in fac))
+            kind, epsilon = "ext_spai", 0.0
+        else:
+            self.L = [_as_device_matrix(M, self.dtype, block_size, self.ctx) for M in Ls] if needs_L else None
         self.n = [M.n for M in self.A]
         self.epsilon = float(epsilon)
         k = len(self.A)
         ha = (C.c_void_p * k)(*[M.handle.value for M in self.A])
-        hl = (C.c_void_p * k)(*[M.handle.value for M in self.L])
+        hl = (C.c_void_p * k)(*[M.handle.value for M in self.L]) if self.L is not None else None
         h = C.c_void_p()
-        _lib.call("lspcg_batch_create", self.ctx.handle, k, ha, hl, self.epsilon, C.byref(h))
+        _lib.call("lspcg_batch_create_precond", self.ctx.handle, k, ha, hl, _lib.PRECOND[kind], self.epsilon,
+                  C.byref(h))
         self.handle = h
 
     def __del__(self):

@@ -9,7 +9,9 @@ Same names, arguments, return values and error behaviour as the reference:
 * ``get_pcg_iter_time``          -- validate.py:89-121 (ext_spai, never raises)
 * ``get_pcg_scaled_iter_time``   -- validate.py:124-160 (ext_spai_scaled)
 * ``get_pcg_iter_time_batch``    -- not in the reference: ``get_pcg_iter_time`` over a window
-  of independent systems solved as one lockstep batch
+  of independent systems solved as one lockstep batch; its twins
+  ``get_pcg_scaled_iter_time_batch`` (ext_spai_scaled) and ``get_cg_iter_time_batch`` (none /
+  diagonal / ainv)
 * ``get_pcg_iter_time_scipy`` / ``get_pcg_diagonal_iter_time_scipy`` /
   ``get_pcg_scaled_iter_time_scipy`` / ``get_cg_iter_time_scipy`` -- validate.py:163-341, the
   reference's host (scipy) restatements, re-exported from ``cpu_rows`` (host comparison rows
@@ -197,30 +199,45 @@ def get_pcg_iter_time(A, gt, spai, epsilon: float, rtol=1e-6, max_iter=0, repeat
                         dot_order, dot_threads)
 
 
-def get_pcg_iter_time_batch(As, gts, spais, epsilon: float, rtol=1e-6, max_iter=0, dtype=np.float64,
-                            infos: Optional[list] = None, repeat: int = 1) -> List[Tuple[float, float, float]]:
-    """get_pcg_iter_time over a window of independent systems solved as ONE lockstep batch
-    (linalg.BatchedConjugateGradient; the reference calls get_pcg_iter_time once per sample,
-    infer.py:322).  Per system ``(iters, prec_s, solve_s)``: the batch's setup (block-diagonal
-    copy, Lᵀ and views: host wall) and device solve time split evenly over its systems, the solve
-    averaged over ``repeat`` solves from x0 = 0 like get_pcg_iter_time (validate.py:111-121).  A
-    window without a SELL view (irregular rows) is solved one system at a time instead, on the GPU."""
+def _batch_generic(kind, As, gts, spais, epsilon, rtol, max_iter, dtype, infos, repeat, single, errors=None):
+    """A window of independent systems as ONE lockstep batch of preconditioner ``kind``
+    (linalg.BatchedConjugateGradient).  Per system ``(iters, prec_s, solve_s)``: the batch's setup
+    (block-diagonal copy, Lᵀ / AINV factors and views: host wall) and device solve time split evenly
+    over its systems, the solve averaged over ``repeat`` solves from x0 = 0.  A window without a
+    SELL view (irregular rows), or one in which an AINV(0) factorisation breaks down, is solved one
+    system at a time instead, on the GPU, by ``single(j, A, L, info)`` -- every system then gets
+    what the sequential path gives it.  ``errors`` (a list, one slot per system): the three baseline kinds'
+    "CG did not converge" of get_cg_iter_time per system -- system j's entry is then None and
+    ``errors[j]`` the RuntimeError; without the list the first such error is raised."""
     Ads = [_prepare(A, dtype) for A in As]
-    Lds = [L if isinstance(L, DeviceMatrix) else _prepare(L, dtype) for L in spais]
+    Lds = None if spais is None else [L if isinstance(L, DeviceMatrix) else _prepare(L, dtype) for L in spais]
     bs = [_device_rhs(A, gt) for A, gt in zip(Ads, gts)]
     k = len(Ads)
+    raises = kind in ("none", "diagonal", "ainv")  # get_cg_iter_time's rule (validate.py:84-85)
+
+    def fail(j, e):
+        if errors is None:
+            raise e
+        errors[j] = e
+        return None
+
     try:
         t0 = time.perf_counter()
-        B = BatchedConjugateGradient(Ads, Lds, epsilon, dtype=dtype)
+        B = BatchedConjugateGradient(Ads, Lds, epsilon, dtype=dtype, preconditioner=kind)
         prec = time.perf_counter() - t0
     except _lib.LspcgError as e:
-        if e.code != _lib.ERR_UNSUPPORTED:
+        if e.code not in (_lib.ERR_UNSUPPORTED, _lib.ERR_BREAKDOWN):
             raise
         out = []
         for j in range(k):
             info = {} if infos is not None else None
-            out.append(get_pcg_iter_time(Ads[j], gts[j], Lds[j], epsilon, rtol, max_iter, repeat, dtype,
-                                         device="cuda", info=info))
+            try:
+                out.append(single(j, Ads[j], None if Lds is None else Lds[j], info))
+            except RuntimeError as err:
+                if not raises:
+                    raise
+                out.append(fail(j, err))
+                continue
             if infos is not None:
                 infos[j].update(info)
         return out
@@ -232,10 +249,51 @@ def get_pcg_iter_time_batch(As, gts, spais, epsilon: float, rtol=1e-6, max_iter=
     t /= max(1, int(repeat))
     out = []
     for j, (it, conv) in enumerate(res):
+        if raises and it >= (max_iter if max_iter > 0 else Ads[j].n):
+            out.append(fail(j, RuntimeError("CG did not converge")))
+            continue
         if infos is not None:
             infos[j].update(x=xs[j], rel_res=relative_residual(Ads[j], xs[j], bs[j]), converged=bool(conv), iters=it)
         out.append((float(it), prec / k, t / k))
     return out
+
+
+def get_pcg_iter_time_batch(As, gts, spais, epsilon: float, rtol=1e-6, max_iter=0, dtype=np.float64,
+                            infos: Optional[list] = None, repeat: int = 1) -> List[Tuple[float, float, float]]:
+    """get_pcg_iter_time over a window of independent systems solved as ONE lockstep batch
+    (linalg.BatchedConjugateGradient; the reference calls get_pcg_iter_time once per sample,
+    infer.py:322).  Per system ``(iters, prec_s, solve_s)``: the batch's setup (block-diagonal
+    copy, Lᵀ and views: host wall) and device solve time split evenly over its systems, the solve
+    averaged over ``repeat`` solves from x0 = 0 like get_pcg_iter_time (validate.py:111-121).  A
+    window without a SELL view (irregular rows) is solved one system at a time instead, on the GPU."""
+    return _batch_generic("ext_spai", As, gts, spais, epsilon, rtol, max_iter, dtype, infos, repeat,
+                          lambda j, A, L, info: get_pcg_iter_time(A, gts[j], L, epsilon, rtol, max_iter, repeat, dtype,
+                                                                  device="cuda", info=info))
+
+
+def get_pcg_scaled_iter_time_batch(As, gts, spais, epsilon: float, rtol=1e-6, max_iter=0, dtype=np.float64,
+                                   infos: Optional[list] = None, repeat: int = 1) -> List[Tuple[float, float, float]]:
+    """get_pcg_scaled_iter_time over a window solved as one lockstep batch: the twin of
+    get_pcg_iter_time_batch for ext_spai_scaled (the same return shape and fall-back)."""
+    return _batch_generic("ext_spai_scaled", As, gts, spais, epsilon, rtol, max_iter, dtype, infos, repeat,
+                          lambda j, A, L, info: get_pcg_scaled_iter_time(A, gts[j], L, epsilon, rtol, max_iter, repeat,
+                                                                         dtype, device="cuda", info=info))
+
+
+def get_cg_iter_time_batch(As, gts, method: str, rtol=1e-6, max_iter=0, dtype=np.float64,
+                           infos: Optional[list] = None, repeat: int = 1,
+                           errors: Optional[list] = None) -> List[Optional[Tuple[float, float, float]]]:
+    """get_cg_iter_time (method none / diagonal / ainv) over a window solved as one lockstep batch;
+    the return shape and the fall-back of get_pcg_iter_time_batch.  A system that reaches max_iter
+    raises ``RuntimeError("CG did not converge")`` as get_cg_iter_time does; with ``errors`` (a list
+    with one slot per system) the error is stored in the system's slot instead, its entry is None
+    and the other systems keep their results.  ``"ic"`` has no lockstep form (ValueError)."""
+    if method not in ("none", "diagonal", "ainv"):
+        raise ValueError(f"method {method!r} has no lockstep batch; expected none / diagonal / ainv")
+    return _batch_generic(method, As, gts, None, 0.0, rtol, max_iter, dtype, infos, repeat,
+                          lambda j, A, L, info: get_cg_iter_time(A, gts[j], rtol, max_iter, dtype, repeat,
+                                                                 device="cuda", method=method, info=info),
+                          errors=errors)
 
 
 def get_pcg_scaled_iter_time(A, gt, spai, epsilon: float, rtol=1e-6, max_iter=0, repeat=1, dtype=np.float64,

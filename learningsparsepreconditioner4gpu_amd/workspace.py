@@ -330,3 +330,12 @@ class ScaledInferenceWorkspace(SimpleInferenceWorkspace):
         L = self._assemble(s, boo, block_output)
         L.scale_columns_(s.rsqrt_diag.reshape(-1).to(torch.float64))
         return (L.to_scipy().tocsr() if return_scipy else L), dt
+
+    def inference_step_batch(self, samples, block_output: Optional[bool] = None):
+        """The window's one forward, every L_k then scaled by its own sample's columns as
+        inference_step scales it (the same bits)."""
+        ss = [s if s.x.is_cuda else s.to(self.device) for s in samples]
+        Ls, dt = super().inference_step_batch(ss, block_output)
+        for L, s in zip(Ls, ss):
+            L.scale_columns_(s.rsqrt_diag.reshape(-1).to(torch.float64))
+        return Ls, dt
