@@ -190,6 +190,25 @@ int lspcg_solver_set_ic_factor(lspcg_solver* s, const lspcg_mat* L, double* t_pr
  * run the whole loop in one single-workgroup launch -- same bits as the multi-kernel schedule. */
 int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int64_t max_iter,
                        int64_t* iters, double* res_hist, double* t_solve_ms);
+/* Solve A X = B for nrhs = 1..8 right-hand sides of the one system in one lockstep loop (heat time
+ * steps on a fixed mesh, load cases, a repeated sample).  B, X: device arrays
+ * [n][nrhs], row-major and contiguous, of the solver's dtype; X holds x0 on entry and the
+ * solutions on return.  Column j comes out as lspcg_solver_solve returns it for (B[:,j], X[:,j])
+ * alone on this solver: scipy cg's recurrence with the column's own scalars, top-of-loop test,
+ * count, history and status (count, status and history equal; iterate within the compensated
+ * dots' rounding).  A zero column is done at the init, a column with a non-finite residual stops
+ * alone, and a finished column is frozen while the others run.  The columns share every launch
+ * and every load of A, L and Lᵀ: the vectors are stored interleaved [n][Kp], Kp = 2, 4 or 8.
+ * iters[j], status[j] (LSPCG_OK / LSPCG_NOT_CONVERGED) and res_hist[j] (host arrays of max_iter + 2
+ * entries; res_hist or any entry may be NULL) describe column j as lspcg_batch_solve reports its
+ * systems; max_iter <= 0 means n.  Returns LSPCG_OK when every column converged,
+ * LSPCG_NOT_CONVERGED when any reached max_iter.
+ * LSPCG_ERR_ARG: nrhs outside 1..8.  LSPCG_ERR_UNSUPPORTED (the message names the reason): any
+ * preconditioner but LSPCG_PRECOND_EXT_SPAI / _EXT_SPAI_SCALED, block size 3, the OpenBLAS dot
+ * order, a reordered solver, or iteration views (lspcg_solver_views) other than SELL-DIA (1) and
+ * SELL-64 with 16- or 32-bit columns (16, 32).  nrhs == 1 is lspcg_solver_solve. */
+int lspcg_solver_solve_multi(lspcg_solver* s, int nrhs, const void* B, void* X, double rtol, int64_t max_iter,
+                             int64_t* iters, int32_t* status, double* const* res_hist, double* t_solve_ms);
 /* Measurement only (bench.py): `iters` iterations of the split ext_spai schedule from x0 = 0,
  * each of the five launches bracketed by HIP events on the solver stream (no graph, no
  * convergence stop); kernel_ms[0..4] = mean device time of KA (t = Lᵀr), KB (z = Lt + εr, ρ),

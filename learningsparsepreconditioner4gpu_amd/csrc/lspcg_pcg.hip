@@ -679,7 +679,10 @@ int lspcg_solver_set_spai(lspcg_solver* s, const lspcg_mat* L, double epsilon, d
   s->L = L;
   s->eps = epsilon;
   // graphs capture the views' addresses and ε: drop them unless the new L kept every one of them
-  if (!(graph_key(s) == key_before)) s->graphs.clear();
+  if (!(graph_key(s) == key_before)) {
+    s->graphs.clear();
+    multi_clear_graphs(s);
+  }
   return LSPCG_OK;
 }
 
@@ -734,6 +737,7 @@ static int install_ic(lspcg_solver* s, const lspcg_mat* given, double* t_prec_ms
   LSPCG_HIP(hipEventElapsedTime(&ms, s->ev_t0, s->ev_t1));
   if (t_prec_ms) *t_prec_ms = ms;
   s->graphs.clear();
+  multi_clear_graphs(s);
   return LSPCG_OK;
 }
 
@@ -879,6 +883,7 @@ int lspcg_solver_set_dot_order(lspcg_solver* s, int order, int threads) {
   s->split = s->split_ok && order == LSPCG_DOT_COMPENSATED;
   setup_split_cg(s);
   s->graphs.clear();
+  multi_clear_graphs(s);
   return LSPCG_OK;
 }
 
@@ -961,6 +966,7 @@ int lspcg_solver_destroy(lspcg_solver* s) {
   (void)hipSetDevice(s->ctx->device);
   (void)hipStreamSynchronize(s->stream);
   s->graphs.clear();
+  multi_destroy(s);
   for (void* v : {s->x, s->b, s->r, s->z, s->t, s->p, s->d}) (void)hipFree(v);
   if (s->q != s->t) (void)hipFree(s->q);
   (void)hipFree(s->S);

@@ -539,6 +539,178 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sdia(SdiaArgs<VT> a, Pro pro,
   finish_epi_dots<Epi>(d, epi);
 }
 
+// ---- K right-hand sides at once (lspcg_multi.hip; DESIGN.md §6 "Several right-hand sides") ----
+// The vectors are interleaved [n][K]: entry (row, column k) at row * K + k, so the K entries one
+// slot gathers are contiguous -- one load of K * sizeof(T) bytes in 16-B parts (8 B for two floats).
+template <typename T, int K>
+struct RowK {
+  static constexpr int W = K * sizeof(T) >= 16 ? 16 / int(sizeof(T)) : K;  // entries per load
+  using V = T __attribute__((ext_vector_type(W)));
+  __device__ static __forceinline__ void load(const T* p, T (&v)[K]) {
+#pragma unroll
+    for (int c = 0; c < K / W; ++c) {
+      const V a = *(const __attribute__((address_space(1))) V*)(p + c * W);
+#pragma unroll
+      for (int w = 0; w < W; ++w) v[c * W + w] = a[w];
+    }
+  }
+  __device__ static __forceinline__ void store(T* p, const T (&v)[K]) {
+#pragma unroll
+    for (int c = 0; c < K / W; ++c) {
+      V a;
+#pragma unroll
+      for (int w = 0; w < W; ++w) a[w] = v[c * W + w];
+      *(__attribute__((address_space(1))) V*)(p + c * W) = a;
+    }
+  }
+};
+
+// SELL-DIA SpMV of K interleaved vectors: k_spmv_sdia with K accumulators per lane.  A slot's
+// value, offset and mask bit are loaded once and applied to the K entries of the gathered row;
+// per column the slots are added in k_spmv_sdia's order, so every column's row sums are the
+// single-vector kernel's bit for bit.  The epilogue's row() takes the K row sums; NDOT counts
+// all of its dots (K per reduced quantity).
+template <typename T, typename VT, int K, int SB, int TH, class Pro, class Epi>
+__global__ void __launch_bounds__(TH) k_spmm_sdia(SdiaArgs<VT> a, const T* __restrict__ x, Pro pro, Epi epi) {
+  constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t ntiles = (a.n + TH - 1) / TH;
+  int32_t g0 = 0, g1 = 0;
+  unsigned msk = 0;
+  int32_t dct[kSdiaMax];
+  auto meta = [&](int64_t sl) {
+    g0 = a.gp[sl];
+    g1 = a.gp[sl + 1];
+    msk = gld(a.mask + kSellC * sl + lane);
+    const int32_t* dp = a.dict + kSdiaMax * sl;
+#pragma unroll
+    for (int j = 0; j < kSdiaMax; ++j) dct[j] = dp[j];
+  };
+  {
+    const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
+    if (int64_t(blockIdx.x) < ntiles && s < a.ns) meta(s);
+  }
+  if (pro.exit()) return;
+  DD d[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) d[j] = dd_zero();
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t s = tile * (TH / 64) + w;
+    const int64_t i = tile * TH + threadIdx.x;
+    if (s < a.ns) {  // wave-uniform
+      if (tile != int64_t(blockIdx.x)) meta(s);
+      const int nd = g1 - g0;
+      const int32_t base = int32_t(s * kSellC);
+      const int32_t row = base + lane;
+      T acc[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = T(0);
+#pragma unroll
+      for (int j0 = 0; j0 < kSdiaMax; j0 += SB) {
+        if (j0 >= nd) break;  // wave-uniform
+        VT v[SB];
+        T xv[SB][K];
+        bool m[SB];
+#pragma unroll
+        for (int u = 0; u < SB; ++u) {
+          const int j = j0 + u;
+          m[u] = (j < nd) && ((msk >> j) & 1u);
+          const int32_t c = m[u] ? row + dct[j] : base;
+          v[u] = gld(a.vals + kSellC * int64_t(g0 + min(j, nd - 1)) + lane);
+          RowK<T, K>::load(x + int64_t(c) * K, xv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < SB; ++u)
+          if (m[u]) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[k] = acc[k] + T(v[u]) * xv[u][k];
+          }
+      }
+      if (i < a.n) epi.row(i, acc, d);
+    }
+  }
+  finish_epi_dots<Epi>(d, epi);
+}
+
+// SELL-64 SpMV (16-bit offsets or int32 columns) of K interleaved vectors: k_spmv_sell with K
+// accumulators per lane, QB groups of 4 entries per batch, the same slot order per column.
+template <typename T, typename VT, typename CT, int K, int QB, int TH, class Pro, class Epi>
+__global__ void __launch_bounds__(TH) k_spmm_sell(SellArgs<VT, CT> a, const T* __restrict__ x, Pro pro, Epi epi) {
+  static_assert(std::is_same<CT, int16_t>::value || std::is_same<CT, int32_t>::value, "16-bit offsets or int32 columns");
+  constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
+  constexpr bool C16 = std::is_same<CT, int16_t>::value;
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int64_t ntiles = (a.n + TH - 1) / TH;
+  int32_t gb[2] = {0, 0};
+  if (int64_t(blockIdx.x) * (TH / 64) + w < a.ns) {
+    gb[0] = a.gp[int64_t(blockIdx.x) * (TH / 64) + w];
+    gb[1] = a.gp[int64_t(blockIdx.x) * (TH / 64) + w + 1];
+  }
+  if (pro.exit()) return;
+  DD d[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) d[j] = dd_zero();
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t s = tile * (TH / 64) + w;
+    const int64_t i = tile * TH + threadIdx.x;
+    if (s < a.ns) {  // wave-uniform
+      if (tile != int64_t(blockIdx.x)) {
+        gb[0] = a.gp[s];
+        gb[1] = a.gp[s + 1];
+      }
+      const int32_t g0 = gb[0];
+      const int nq = gb[1] - g0;
+      const int32_t base = int32_t(s * kSellC);
+      const VT* vp = a.vals + 256 * int64_t(g0) + 4 * lane;
+      const CT* cp = a.col + 256 * int64_t(g0) + 4 * lane;
+      T acc[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = T(0);
+      for (int q0 = 0; q0 < nq; q0 += QB) {
+        VT v[QB][4];
+        int c[QB][4];
+        bool m[QB][4];
+#pragma unroll
+        for (int u = 0; u < QB; ++u) {
+          const int q = min(q0 + u, nq - 1);
+          Vec4Ld<VT>::load(vp + 256 * q, v[u]);
+          int o[4];
+          if constexpr (C16) {
+            const i16x4 cc = *(const __attribute__((address_space(1))) i16x4*)(cp + 256 * q);
+            o[0] = cc.x; o[1] = cc.y; o[2] = cc.z; o[3] = cc.w;
+          } else {
+            const i32x4 cc = *(const __attribute__((address_space(1))) i32x4*)(cp + 256 * q);
+            o[0] = cc.x; o[1] = cc.y; o[2] = cc.z; o[3] = cc.w;
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bool real = C16 ? o[j] != kSellPad16 : o[j] >= 0;
+            m[u][j] = real && (q0 + u < nq);
+            c[u][j] = real ? (C16 ? base + o[j] : o[j]) : base;  // padding gathers the slice's first row
+          }
+        }
+        T xv[QB][4][K];
+#pragma unroll
+        for (int u = 0; u < QB; ++u)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) RowK<T, K>::load(x + int64_t(c[u][j]) * K, xv[u][j]);
+#pragma unroll
+        for (int u = 0; u < QB; ++u)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (m[u][j]) {
+#pragma unroll
+              for (int k = 0; k < K; ++k) acc[k] = acc[k] + T(v[u][j]) * xv[u][j][k];
+            }
+      }
+      if (i < a.n) epi.row(i, acc, d);
+    }
+  }
+  finish_epi_dots<Epi>(d, epi);
+}
+
 // position of plane v of lane `lane` inside a BSELL-64 slot (see SellPattern)
 template <typename VT>
 __host__ __device__ constexpr int bsell_pos(int v, int lane) {
@@ -855,6 +1027,38 @@ inline void launch_spmv_sell_cfg(const SellPattern& P, const void* vals, Gx gx, 
   else if (P.col_bits == 16) launch_spmv_sell_th<T, VT, int16_t, kSellWG>(P, vals, gx, pro, epi, st, one_tile_per_wg);
   else if (P.col_bits == 8) launch_spmv_sell_th<T, VT, uint8_t, kSellWG>(P, vals, gx, pro, epi, st, one_tile_per_wg);
   else launch_spmv_sell_th<T, VT, int32_t, kSellWG>(P, vals, gx, pro, epi, st, one_tile_per_wg);
+}
+
+// K-vector launches.  SELL-DIA batches 8 / 8 / 4 slots for K = 2 / 4 / 8 (<= 32 vector entries of
+// K * sizeof(T) bytes in flight per lane: mid-size systems run one wave per SIMD, so a lane's own
+// loads in flight, not occupancy, hide the latency there; half as many slots measured a few per
+// cent slower on Poisson 256^2); SELL-64 batches two 4-entry groups for K = 2 and one for K = 4, 8.
+// Register counts and occupancy: DESIGN.md §6.  Scalar patterns of kind SELL-DIA, 16-bit offsets
+// or int32 columns only; false for any other kind (nothing is launched).
+template <int K>
+constexpr int spmm_sb() { return K == 8 ? 4 : 8; }
+template <int K>
+constexpr int spmm_qb() { return K == 2 ? 2 : 1; }
+inline bool spmm_supported(const SellPattern& P) {
+  return P.bs == 1 && (P.col_bits == 1 || P.col_bits == 16 || P.col_bits == 32);
+}
+template <typename T, typename VT, int K, class Pro, class Epi>
+inline bool launch_spmm_cfg(const SellPattern& P, const void* vals, const T* x, Pro pro, Epi epi, hipStream_t st) {
+  if (!spmm_supported(P)) return false;
+  const int64_t grid = std::min<int64_t>((P.nb + kSellWG - 1) / kSellWG, sell_cap(Epi::NDOT > 0));
+  if (grid <= 0) return true;
+  const dim3 g{unsigned(grid)}, b{kSellWG};
+  if (P.col_bits == 1) {
+    SdiaArgs<VT> a{P.n, P.ns, P.gp, static_cast<const uint16_t*>(P.col), P.dict, static_cast<const VT*>(vals)};
+    hipLaunchKernelGGL((k_spmm_sdia<T, VT, K, spmm_sb<K>(), kSellWG, Pro, Epi>), g, b, 0, st, a, x, pro, epi);
+  } else if (P.col_bits == 16) {
+    SellArgs<VT, int16_t> a{P.n, P.ns, P.gp, static_cast<const int16_t*>(P.col), P.rowptr, static_cast<const VT*>(vals)};
+    hipLaunchKernelGGL((k_spmm_sell<T, VT, int16_t, K, spmm_qb<K>(), kSellWG, Pro, Epi>), g, b, 0, st, a, x, pro, epi);
+  } else {
+    SellArgs<VT, int32_t> a{P.n, P.ns, P.gp, static_cast<const int32_t*>(P.col), P.rowptr, static_cast<const VT*>(vals)};
+    hipLaunchKernelGGL((k_spmm_sell<T, VT, int32_t, K, spmm_qb<K>(), kSellWG, Pro, Epi>), g, b, 0, st, a, x, pro, epi);
+  }
+  return true;
 }
 
 }  // namespace lspcg

@@ -65,6 +65,8 @@ struct IterationGraphs {
   }
 };
 
+struct MultiWs;  // lspcg_solver_solve_multi's workspace (lspcg_multi.hip)
+
 }  // namespace lspcg
 
 struct lspcg_solver {
@@ -135,9 +137,15 @@ struct lspcg_solver {
   int dot_order = LSPCG_DOT_COMPENSATED;  // lspcg_solver_set_dot_order
   int dot_threads = 1;
   double* ob_part = nullptr;  // [3 dots x kObMaxThreads chunks] parity-mode chunk totals (k_dot_openblas_item)
+  lspcg::MultiWs* multi = nullptr;  // K-wide vectors, states and graphs of solve_multi: allocated on first use
 };
 
 namespace lspcg {
+
+// lspcg_multi.hip: drop solve_multi's captured graphs (whenever the solver drops its own: they hold
+// the same views, ε and d by value); free its workspace (lspcg_solver_destroy)
+void multi_clear_graphs(lspcg_solver* s);
+void multi_destroy(lspcg_solver* s);
 
 // lspcg_solver_create with the batch's switches: no SELL-DIA views (a window of one-workgroup
 // solves), no reordering (lspcg_pcg.hip)
