@@ -2,7 +2,7 @@
 // A window of independent systems is laid out block-diagonally, every system's rows padded to
 // whole SpMV row tiles (256 block rows), and ONE launch per phase covers all of them.  The two
 // ext_spai kinds run the split schedule's five launches (KA, KB, UP, KC, UR; the scaled kind with
-// EpiT / EpiZ's divisions by d = diag(A)); no preconditioner and the diagonal one have no KA / KB
+// EpiT / RowZ's divisions by d = diag(A)); no preconditioner and the diagonal one have no KA / KB
 // and run three (UP, KC, UR), UR also reducing the next iteration's dots (‖r‖², ρ = r·z) per
 // system.  In every launch
 //   * one row tile per workgroup (launch_spmv_sell_cfg one_tile_per_wg), so a workgroup's dot
@@ -19,7 +19,9 @@
 // would put NaN into the system's dots.
 //
 // The window is solved by an lspcg_solver of the block-diagonal system (lspcg_solver.hpp, created
-// in lspcg_pcg.hip); the loop's shared device code is in lspcg_pcg_kernels.hpp.
+// in lspcg_pcg.hip).  The epilogues' row bodies and the one-workgroup solve are those of
+// lspcg_pcg_kernels.hpp, every state transition is lspcg_pcg_step.hpp's; this unit adds the
+// per-system way of finishing the dots and the elementwise kernels of one tile per workgroup.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,10 +51,8 @@ struct ProTile {
 };
 
 // Per-system last-arriver reduction of a batched launch's N dots: each workgroup (= one row tile)
-// publishes its tile total (sc1 stores, drained, then relaxed agent-scope adds -- MI355X_MICROARCH.md
-// "Valid forms", table row 1, as grid_reduce_dd); the adds go to a two-level ticket (groups of
-// kTicketGroup tiles, then the system's top line: <= 32 serialised arrivals per line instead of a
-// system's few hundred -- the fan-in price), and the system's last arriving tile sums the system's
+// publishes its tile total and arrives on the system's two-level ticket (publish_dd, ticket_arrive:
+// <= 32 serialised arrivals per line instead of a system's few hundred -- the fan-in price), and the system's last arriving tile sums the system's
 // tile totals in tile order (fixed tree: the result does not depend on which tile came last);
 // thread 0 then runs fin(sys, values).  The elementwise launches read finished per-system scalars.
 // sys_reduce_tiles is the reduction itself over tiles [t0, t0 + nt) of system `sys` in the launch's
@@ -66,22 +66,9 @@ __device__ __forceinline__ void sys_reduce_tiles(DD (&v)[N], double* partials, u
   block_reduce_dd<N>(v, lds);
   const int64_t tile = blockIdx.x;
   if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      st_agent_f64(&partials[(size_t(tile) * N + j) * 2 + 0], v[j].s);
-      st_agent_f64(&partials[(size_t(tile) * N + j) * 2 + 1], v[j].c);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned g = unsigned(tile - t0) / kTicketGroup;
-    const unsigned gsize = min(unsigned(kTicketGroup), unsigned(nt) - g * kTicketGroup);
-    const unsigned ng = (unsigned(nt) + kTicketGroup - 1) / kTicketGroup;
-    unsigned* gt = top + size_t(kTicketStride) * (1 + g);
-    int last = 0;
-    if (__hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1) {
-      __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = __hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ng - 1;
-      if (last) __hip_atomic_store(top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    publish_dd<N>(&partials[size_t(tile) * N * 2], v);
+    const bool last = ticket_arrive(top, unsigned(tile - t0), unsigned(nt));
+    if (last) ticket_reset(top);  // at once: the partials, not the ticket, carry what the sum below reads
     s_last = last;
   }
   __syncthreads();
@@ -92,8 +79,7 @@ __device__ __forceinline__ void sys_reduce_tiles(DD (&v)[N], double* partials, u
   for (int b = threadIdx.x; b < nt; b += blockDim.x) {
 #pragma unroll
     for (int j = 0; j < N; ++j) {
-      const size_t k = (size_t(t0 + b) * N + j) * 2;
-      acc[j] = dd_add(acc[j], DD{ld_agent_f64(&partials[k]), ld_agent_f64(&partials[k + 1])});
+      acc[j] = dd_add(acc[j], read_dd(&partials[(size_t(t0 + b) * N + j) * 2]));
     }
   }
   __syncthreads();
@@ -114,78 +100,43 @@ __device__ __forceinline__ void batch_sys_reduce(DD (&v)[N], double* partials, u
   sys_reduce_tiles<N>(v, partials, tickets + size_t(kTicketStride) * m.tk0[sys], sys, t0, m.tile0[sys + 1] - t0, fin);
 }
 
-// scipy's top-of-loop test for a system at iteration k with ‖r_k‖² = rr (ProCheck's codes)
-template <typename T>
-__device__ __forceinline__ int loop_test(int64_t k, int64_t max_iter, double rr, double atol) {
-  if (k >= max_iter) return 2;
-  const double rn = double(tsqrt<T>(T(rr)));
-  if (rn < atol) return 1;
-  if (!(rn == rn) || rn == INFINITY) return 3;
-  return 0;
-}
-
-// the system's initial state from its init dots ‖r_0‖², ‖b‖² (, ρ_0 = r_0·z_0 for Jacobi): EpiResid::fin
-template <typename T, int PRE>
-__device__ __forceinline__ void init_state(PcgState* St, const double* v) {
-  St->rr = round_to<T>(v[0]);
-  St->bb = round_to<T>(v[1]);
-  const double bn = double(tsqrt<T>(T(St->bb)));
-  St->atol = fmax(0.0, St->rtol * bn);
-  St->rho = PRE == LSPCG_PRECOND_DIAGONAL ? round_to<T>(v[2]) : St->rr;
-  St->alpha = 0.0;
-  St->iter = 0;
-  St->done = (bn == 0.0) ? 1 : 0;
-  if (St->hist) St->hist[0] = double(tsqrt<T>(T(St->rr)));
-}
-
-// init: r_0 = b - A x0 ; ‖r_0‖², ‖b‖² -> the system's initial state (EpiResid::fin).  PRE = NONE /
-// DIAGONAL (three-launch schedule): Jacobi's z_0 = r_0/d and ρ_0 as EpiResid<T, DIAGONAL>, and the
-// last arriver also runs iteration 0's top-of-loop test, which the ext_spai kinds leave to KB
-template <typename T, int PRE = LSPCG_PRECOND_EXT_SPAI>
-struct EpiResidB {
-  static constexpr bool CG = PRE == LSPCG_PRECOND_NONE || PRE == LSPCG_PRECOND_DIAGONAL;
-  static constexpr int NDOT = PRE == LSPCG_PRECOND_DIAGONAL ? 3 : 2;
+// Finishing way 3 of an epilogue's dots (lspcg_pcg_kernels.hpp has the row bodies and the other
+// two): the per-system last arriver, which runs the composed epilogue's static fin(state, values).
+struct BySystem {
   static constexpr bool CUSTOM_FINISH = true;
-  T* r;
-  const T* b;
   PcgState* S;
   double* partials;
   unsigned* tickets;
   BatchMap m;
-  const T* d = nullptr;
-  T* z = nullptr;
-  __device__ __forceinline__ void prepare() {}
-  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    const T bi = gld(b + i);
-    const T ri = bi - s;
-    gst(r + i, ri);
-    dd_fma(dots[0], double(ri), double(ri));
-    dd_fma(dots[1], double(bi), double(bi));
-    if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
-      const T zi = ri / gld(d + i);
-      gst(z + i, zi);
-      dd_fma(dots[2], double(ri), double(zi));
-    }
-  }
-  __device__ __forceinline__ void finish(DD (&dd)[NDOT]) const {
-    PcgState* Sb = S;
-    batch_sys_reduce<NDOT>(dd, partials, tickets, m, [Sb](int sys, const double* v) {
-      PcgState* St = Sb + sys;
-      init_state<T, PRE>(St, v);
-      if constexpr (CG) {
-        if (!St->done) {
-          const int code = loop_test<T>(0, St->max_iter, St->rr, St->atol);
-          if (code) St->done = code;
-        }
-      }
-    });
+};
+template <class Epi>
+__device__ __forceinline__ void finish_by_system(const Epi& e, DD (&dd)[Epi::NDOT]) {
+  PcgState* Sb = e.S;
+  batch_sys_reduce<Epi::NDOT>(dd, e.partials, e.tickets, e.m, [Sb](int sys, const double* v) { Epi::fin(Sb + sys, v); });
+}
+
+// init: r_0 = b - A x0 ; ‖r_0‖², ‖b‖² -> the system's initial state.  PRE = NONE / DIAGONAL
+// (three-launch schedule): Jacobi's z_0 = r_0/d and ρ_0, and the last arriver also runs iteration
+// 0's top-of-loop test, which the ext_spai kinds leave to KB
+template <typename T, int PRE = LSPCG_PRECOND_EXT_SPAI>
+struct EpiResidB : RowResid<T, PRE>, BySystem {
+  static constexpr bool CG = PRE == LSPCG_PRECOND_NONE || PRE == LSPCG_PRECOND_DIAGONAL;
+  static constexpr int NDOT = RowResid<T, PRE>::NDOT;
+  __device__ __forceinline__ void finish(DD (&dd)[NDOT]) const { finish_by_system(*this, dd); }
+  __device__ static __forceinline__ void fin(PcgState* St, const double* v) {
+    const double rtol = St->rtol;
+    double* const hist = St->hist;
+    const int64_t max_iter = CG ? St->max_iter : 0;
+    init_state<T, CG>(St, rtol, hist, v[0], v[1], v[PRE == LSPCG_PRECOND_DIAGONAL ? 2 : 0], max_iter);
   }
 };
 
-// KB: z = L t + ε r ; ρ_k = r·z, ‖r_k‖² -> the system's last arriver keeps ρ_k (EpiZ::fin) and runs
-// scipy's top-of-loop test on ‖r_k‖ (ProCheck / k_update_p_g): every tile of the system has
-// already passed this launch's prologue, so setting `done` here is seen first by UP.
-// SCALED: z = L t + (ε r)/d, EpiZ<T, true>'s expression
+// KB: z = L t + ε r ; ρ_k = r·z, ‖r_k‖² -> the system's last arriver keeps ρ_k and runs scipy's
+// top-of-loop test on ‖r_k‖: every tile of the system has already passed this launch's prologue,
+// so setting `done` here is seen first by UP.
+// (RowZ's body on members of its own, in the kernel-argument order this epilogue was measured with:
+// with RowZ as a base the compiler schedules the SELL-DIA row loop differently, 153.1 vs 150.7 us per
+// launch on a window of 8 x 1 M rows)
 template <typename T, bool SCALED = false>
 struct EpiZB {
   static constexpr int NDOT = 2;
@@ -200,70 +151,31 @@ struct EpiZB {
   const T* d = nullptr;
   __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    const T ri = gld(r + i);
-    T zi;
-    if constexpr (SCALED) zi = s + (eps * ri) / gld(d + i);
-    else zi = s + eps * ri;
-    gst(z + i, zi);
-    dd_fma(dots[0], double(ri), double(zi));
-    dd_fma(dots[1], double(ri), double(ri));
+    RowZ<T, SCALED>{z, r, d, eps}.row(i, s, dots);
   }
-  __device__ __forceinline__ void finish(DD (&d)[2]) const {
-    PcgState* Sb = S;
-    batch_sys_reduce<2>(d, partials, tickets, m, [Sb](int sys, const double* v) {
-      PcgState* St = Sb + sys;
-      St->rho_prev = St->rho;
-      St->rho = round_to<T>(v[0]);
-      const int64_t k = St->iter;
-      double rr = St->rr;  // ‖r_0‖² from the init
-      if (k > 0) {
-        rr = round_to<T>(v[1]);
-        St->rr = rr;
-        if (St->hist) St->hist[k] = double(tsqrt<T>(T(rr)));
-      }
-      int code = 0;
-      if (k >= St->max_iter) {
-        code = 2;
-      } else {
-        const double rn = double(tsqrt<T>(T(rr)));
-        if (rn < St->atol) code = 1;
-        else if (!(rn == rn) || rn == INFINITY) code = 3;
-      }
-      if (code) St->done = code;
-    });
+  __device__ __forceinline__ void finish(DD (&dd)[2]) const { finish_by_system(*this, dd); }
+  __device__ static __forceinline__ void fin(PcgState* St, const double* v) {
+    const int64_t k = St->iter, max_iter = St->max_iter;
+    const double rho_old = St->rho, rr0 = St->rr, atol = St->atol;  // ‖r_0‖² from the init
+    double* const hist = St->hist;
+    const double rrk = keep_z<T>(St, k, rho_old, hist, v[0], v[1]);
+    const int code = loop_test<T>(k, max_iter, k > 0 ? rrk : rr0, atol);
+    if (code) St->done = code;
   }
 };
 
-// KC: q = A p ; π_k = p·q -> α_k = ρ_k/π_k, iteration k+1 (EpiQ<INC>::fin)
+// KC: q = A p ; π_k = p·q -> α_k = ρ_k/π_k, iteration k+1
 template <typename T>
-struct EpiQB {
-  static constexpr int NDOT = 1;
-  static constexpr bool CUSTOM_FINISH = true;
-  T* q;
-  const T* p;
-  PcgState* S;
-  double* partials;
-  unsigned* tickets;
-  BatchMap m;
-  __device__ __forceinline__ void prepare() {}
-  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    gst(q + i, s);
-    dd_fma(dots[0], double(gld(p + i)), double(s));
-  }
-  __device__ __forceinline__ void finish(DD (&d)[1]) const {
-    PcgState* Sb = S;
-    batch_sys_reduce<1>(d, partials, tickets, m, [Sb](int sys, const double* v) {
-      PcgState* St = Sb + sys;
-      const double pq = round_to<T>(v[0]);
-      St->pq = pq;
-      St->alpha = double(T(St->rho) / T(pq));
-      St->iter = St->iter + 1;
-    });
+struct EpiQB : RowQ<T>, BySystem {
+  __device__ __forceinline__ void finish(DD (&dd)[1]) const { finish_by_system(*this, dd); }
+  __device__ static __forceinline__ void fin(PcgState* St, const double* v) {
+    const int64_t k = St->iter;
+    keep_q<T, true>(St, k, St->rho, v[0]);
   }
 };
 
-// UP: x += α_{k-1} p_{k-1} (k > 0) ; p_k = p_{k-1}β + z with β = ρ_k/ρ_{k-1} (k_update_p_g's
-// expressions), one 256-row tile of one system per workgroup
+// UP: x += α_{k-1} p_{k-1} (k > 0) ; p_k = p_{k-1}β + z with β = ρ_k/ρ_{k-1}, one 256-row tile of
+// one system per workgroup
 template <typename T>
 __global__ void __launch_bounds__(kThreads) k_batch_update_p(BatchMap m, const PcgState* S, const T* __restrict__ z,
                                                              T* __restrict__ p, T* __restrict__ x) {
@@ -289,27 +201,22 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r(BatchMap m, const P
   r[i] = ri - T(St->alpha) * qi;
 }
 
-// The elementwise tile's own dots of the three-launch UR: r_{k+1} = r_k - α q stored, Jacobi's
-// z = r/d stored, dots[0] = ‖r_{k+1}‖², dots[ND - 1] = ρ_{k+1} = r·z (k_update_r's expressions)
+// The elementwise tile's row of the three-launch UR: r_{k+1} = r_k - α q stored, then r_dots_row
+// (dots[0] = ‖r_{k+1}‖², dots[ND - 1] = ρ_{k+1})
 template <typename T, int PRE>
 __device__ __forceinline__ void update_r_row(int64_t i, T ri, T qi, T alpha, T* __restrict__ r,
                                              const T* __restrict__ d, T* __restrict__ z,
                                              DD (&dots)[PRE == LSPCG_PRECOND_DIAGONAL ? 2 : 1]) {
   const T rn = ri - alpha * qi;
   r[i] = rn;
-  dd_fma(dots[0], double(rn), double(rn));
-  if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
-    const T zi = rn / d[i];
-    z[i] = zi;
-    dd_fma(dots[1], double(rn), double(zi));
-  }
+  r_dots_row<T, PRE, false>(i, rn, d, z, dots[0], dots[PRE == LSPCG_PRECOND_DIAGONAL ? 1 : 0]);
 }
 
 // UR of the three-launch schedule (no preconditioner / Jacobi), last-arriver mode: the update, then
 // the per-system reduction over the system's ELEMENTWISE tiles (m.bs per SpMV tile: tickets `tk0`
 // / `tickets` and `partials` are this launch's own, sized for it).  KC's last arriver has already
 // counted the iteration (EpiQB), so the system's last arriver here keeps ‖r_{k+1}‖² and ρ_{k+1}
-// (k_update_r's fin) and runs iteration k+1's top-of-loop test: every tile of the system has read
+// and runs iteration k+1's top-of-loop test: every tile of the system has read
 // `done` and α by then, and UP is the first launch to see the new `done`.
 template <typename T, int PRE>
 __global__ void __launch_bounds__(kThreads) k_batch_update_r_dots(BatchMap m, PcgState* S, const T* __restrict__ q,
@@ -330,13 +237,11 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r_dots(BatchMap m, Pc
   sys_reduce_tiles<ND>(dots, partials, tickets + size_t(kTicketStride) * tk0[sys], sys, t0, nt,
                        [Sb](int s, const double* v) {
                          PcgState* St = Sb + s;
-                         const double rr2 = round_to<T>(v[0]);
-                         St->rr = rr2;
-                         St->rho_prev = St->rho;
-                         St->rho = PRE == LSPCG_PRECOND_DIAGONAL ? round_to<T>(v[ND - 1]) : rr2;
-                         const int64_t it = St->iter;  // k + 1 (EpiQB)
-                         if (St->hist) St->hist[it] = double(tsqrt<T>(T(rr2)));
-                         const int code = loop_test<T>(it, St->max_iter, rr2, St->atol);
+                         const int64_t it = St->iter, max_iter = St->max_iter;  // it = k + 1 (EpiQB)
+                         const double rho_old = St->rho, atol = St->atol;
+                         double* const hist = St->hist;
+                         const double rr2 = keep_r<T, true>(St, it, rho_old, hist, v[0], v[ND - 1]);
+                         const int code = loop_test<T>(it, max_iter, rr2, atol);
                          if (code) St->done = code;
                        });
 }
@@ -346,34 +251,9 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r_dots(BatchMap m, Pc
 // system's tile partials itself (group_sum_dd, one wave for <= 256) ------------------------------
 // init: r_0 = b - A x0 ; per-tile partials of ‖r_0‖², ‖b‖² (PRE = DIAGONAL: + z_0 = r_0/d and ρ_0)
 template <typename T, int PRE = LSPCG_PRECOND_EXT_SPAI>
-struct EpiResidTile {
-  static constexpr int NDOT = PRE == LSPCG_PRECOND_DIAGONAL ? 3 : 2;
-  static constexpr bool GROUPS = true;
-  T* r;
-  const T* b;
-  double* partials;
-  unsigned* ticket;
-  double* group_out;
-  int gsz;
-  const T* d = nullptr;
-  T* z = nullptr;
-  __device__ __forceinline__ void prepare() {}
-  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    const T bi = gld(b + i);
-    const T ri = bi - s;
-    gst(r + i, ri);
-    dd_fma(dots[0], double(ri), double(ri));
-    dd_fma(dots[1], double(bi), double(bi));
-    if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
-      const T zi = ri / gld(d + i);
-      gst(z + i, zi);
-      dd_fma(dots[2], double(ri), double(zi));
-    }
-  }
-  __device__ __forceinline__ void fin(const double*) const {}
-};
+using EpiResidTile = EpiGroups<RowResid<T, PRE>>;
 
-// one workgroup per system: the init state from the system's tile partials (EpiResid::fin)
+// one workgroup per system: the init state from the system's tile partials
 template <typename T, int PRE = LSPCG_PRECOND_EXT_SPAI>
 __global__ void __launch_bounds__(kThreads) k_batch_init(PcgState* S, const int32_t* __restrict__ tile0,
                                                          const double* __restrict__ gi) {
@@ -383,15 +263,18 @@ __global__ void __launch_bounds__(kThreads) k_batch_init(PcgState* S, const int3
   double v[ND];
   group_sum_dd<ND>(gi + size_t(t0) * 2 * ND, t1 - t0, v);
   if (threadIdx.x) return;
-  init_state<T, PRE>(S + sys, v);
+  PcgState* St = S + sys;
+  const double rtol = St->rtol;
+  double* const hist = St->hist;
+  init_state<T>(St, rtol, hist, v[0], v[1], v[PRE == LSPCG_PRECOND_DIAGONAL ? 2 : 0]);
 }
 
-// consumer-sum mode: UP of the split schedule (k_update_p_g) for the tile's system, summing the
-// system's tile partials itself
+// consumer-sum mode: UP of the split schedule for the tile's system, summing the system's tile
+// partials itself
 // CG (three-launch schedule): gz holds UR's per-ELEMENTWISE-tile partials (bs per SpMV tile) of
 // ρ_k, ‖r_k‖² for k > 0 (iteration 0 takes both from the init state), z is r without a
-// preconditioner, and the system's first workgroup leaves ρ_k in the state for UR (rho_k, as
-// k_update_p_g), which overwrites gz
+// preconditioner, and the system's first workgroup leaves ρ_k in the state for UR (rho_k), which
+// overwrites gz
 template <typename T, bool CG = false>
 __global__ void __launch_bounds__(kThreads) k_batch_update_p_sums(BatchMap m, PcgState* S, const double* __restrict__ gz,
                                                              const T* __restrict__ z, T* __restrict__ p,
@@ -411,19 +294,9 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_p_sums(BatchMap m, Pc
   if (done) return;
   const double rho = (!CG || k > 0) ? round_to<T>(v[0]) : St->rho;
   const double rr = k > 0 ? round_to<T>(v[1]) : St->rr;
-  int code = 0;
-  if (k >= St->max_iter) {
-    code = 2;
-  } else {
-    const double rn = double(tsqrt<T>(T(rr)));
-    if (rn < St->atol) code = 1;
-    else if (!(rn == rn) || rn == INFINITY) code = 3;
-  }
+  const int code = loop_test<T>(k, St->max_iter, rr, St->atol);
   if (int64_t(blockIdx.x) == int64_t(t0) * m.bs && threadIdx.x == 0) {
-    if (k > 0) {
-      St->rr = rr;
-      if (St->hist) St->hist[k] = double(tsqrt<T>(T(rr)));
-    }
+    keep_rr<T>(St, k, St->hist, rr);
     if (code) St->done = code;
     else if constexpr (CG) St->rho_k = rho;
   }
@@ -435,7 +308,7 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_p_sums(BatchMap m, Pc
   p[i] = first ? zi : (pi * beta) + zi;
 }
 
-// consumer-sum mode: UR of the split schedule (k_update_r_g) for the tile's system
+// consumer-sum mode: UR of the split schedule for the tile's system
 template <typename T>
 __global__ void __launch_bounds__(kThreads) k_batch_update_r_sums(BatchMap m, PcgState* S, const double* __restrict__ gz,
                                                              const double* __restrict__ gq, const T* __restrict__ q,
@@ -453,16 +326,14 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r_sums(BatchMap m, Pc
   const double pq = round_to<T>(vq[0]);
   const T alpha = T(rho) / T(pq);
   if (int64_t(blockIdx.x) == int64_t(t0) * m.bs && threadIdx.x == 0) {
-    St->rho_prev = St->rho;
-    St->rho = rho;
-    St->pq = pq;
-    St->alpha = double(alpha);
-    St->iter = St->iter + 1;
+    const double rho_old = St->rho;
+    const int64_t k = St->iter;
+    commit_step<T>(St, rho_old, rho, pq, alpha, k + 1);
   }
   r[i] = ri - alpha * qi;
 }
 
-// consumer-sum mode: UR of the three-launch schedule (k_update_r_gd) for the tile's system:
+// consumer-sum mode: UR of the three-launch schedule for the tile's system:
 // α_k = ρ_k/π_k from the state's ρ_k (UP) and KC's tile partials, the update, and this elementwise
 // tile's partials of ρ_{k+1}, ‖r_{k+1}‖² for the next UP (plain stores: read after the kernel boundary)
 template <typename T, int PRE>
@@ -485,11 +356,9 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r_sums_cg(BatchMap m,
   const double pq = round_to<T>(vq[0]);
   const T alpha = T(rho) / T(pq);
   if (int64_t(blockIdx.x) == int64_t(t0) * m.bs && threadIdx.x == 0) {
-    St->rho_prev = St->rho;
-    St->rho = rho;
-    St->pq = pq;
-    St->alpha = double(alpha);
-    St->iter = St->iter + 1;
+    const double rho_old = St->rho;
+    const int64_t k = St->iter;
+    commit_step<T>(St, rho_old, rho, pq, alpha, k + 1);
   }
   DD dots[ND];
 #pragma unroll
@@ -594,25 +463,20 @@ static int launch_it_tiles(lspcg_solver* s, int w, const T* x, Pro pro, Epi epi,
 template <typename T>
 static int enqueue_batch_init(lspcg_batch* bt, hipStream_t st) {
   lspcg_solver* s = bt->s;
-  T* r = static_cast<T*>(s->r);
-  const T* b = static_cast<const T*>(s->b);
-  const T* x = static_cast<const T*>(s->x);
-  const T* d = static_cast<const T*>(s->d);
-  T* z = static_cast<T*>(s->z);
+  const T* x = as<T>(s->x);
   // PRE: EXT_SPAI stands for both ext_spai kinds (their init has no preconditioner part)
   auto go = [&](auto pre) -> int {
     constexpr int PRE = decltype(pre)::value;
+    const RowResid<T, PRE> row{as<T>(s->r), as<T>(s->b), as<T>(s->d), as<T>(s->z)};
     if (bt->sums) {
-      int rc = launch_it_tiles<T>(s, 0, x, ProNone{}, EpiResidTile<T, PRE>{r, b, nullptr, nullptr, bt->gsum, 1, d, z},
-                                  st);
+      int rc = launch_it_tiles<T>(s, 0, x, ProNone{}, EpiResidTile<T, PRE>{row, {nullptr, nullptr, bt->gsum, 1}}, st);
       if (rc) return rc;
-      hipLaunchKernelGGL((k_batch_init<T, PRE>), dim3(bt->nsys), dim3(kThreads), 0, st, bt->S,
-                         static_cast<const int32_t*>(bt->tile0), static_cast<const double*>(bt->gsum));
+      launch(k_batch_init<T, PRE>, dim3(bt->nsys), dim3(kThreads), st, bt->S, bt->tile0, bt->gsum);
       LSPCG_HIP(hipGetLastError());
       return LSPCG_OK;
     }
     return launch_it_tiles<T>(s, 0, x, ProNone{},
-                              EpiResidB<T, PRE>{r, b, bt->S, bt->partials, bt->tickets, batch_map(bt), d, z}, st);
+                              EpiResidB<T, PRE>{row, {bt->S, bt->partials, bt->tickets, batch_map(bt)}}, st);
   };
   if (bt->precond == LSPCG_PRECOND_NONE) return go(std::integral_constant<int, LSPCG_PRECOND_NONE>{});
   if (bt->precond == LSPCG_PRECOND_DIAGONAL) return go(std::integral_constant<int, LSPCG_PRECOND_DIAGONAL>{});
@@ -623,32 +487,25 @@ static int enqueue_batch_init(lspcg_batch* bt, hipStream_t st) {
 template <typename T, int PRE>
 static int enqueue_batch_iteration_cg(lspcg_batch* bt, hipStream_t st) {
   lspcg_solver* s = bt->s;
-  T* x = static_cast<T*>(s->x);
-  T* r = static_cast<T*>(s->r);
-  T* z = static_cast<T*>(s->z);
-  T* p = static_cast<T*>(s->p);
-  T* q = static_cast<T*>(s->q);
-  const T* d = static_cast<const T*>(s->d);
+  T *x = as<T>(s->x), *r = as<T>(s->r), *z = as<T>(s->z), *p = as<T>(s->p), *q = as<T>(s->q);
+  const T* d = as<T>(s->d);
   const T* zp = PRE == LSPCG_PRECOND_NONE ? r : z;  // z = r without a preconditioner
   const BatchMap m = batch_map(bt);
   const ProTile pro{bt->S, m};
-  const dim3 eg(unsigned(bt->ntot / kThreads));
+  const BySystem by{bt->S, bt->partials, bt->tickets, m};
+  const dim3 eg(unsigned(bt->ntot / kThreads)), eb(kThreads);
   int rc = LSPCG_OK;
   if (bt->sums) {
-    hipLaunchKernelGGL((k_batch_update_p_sums<T, true>), eg, dim3(kThreads), 0, st, m, bt->S,
-                       static_cast<const double*>(bt->gz), zp, p, x);
-    rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(p), pro, EpiQG<T>{q, p, nullptr, nullptr, bt->gq, 1}, st);
+    launch(k_batch_update_p_sums<T, true>, eg, eb, st, m, bt->S, bt->gz, zp, p, x);
+    rc = launch_it_tiles<T>(s, 0, p, pro, EpiQG<T>{{q, p}, {nullptr, nullptr, bt->gq, 1}}, st);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_batch_update_r_sums_cg<T, PRE>), eg, dim3(kThreads), 0, st, m, bt->S,
-                       static_cast<const double*>(bt->gq), static_cast<const T*>(q), r, d, z, bt->gz);
-    LSPCG_HIP(hipGetLastError());
-    return LSPCG_OK;
+    launch(k_batch_update_r_sums_cg<T, PRE>, eg, eb, st, m, bt->S, bt->gq, q, r, d, z, bt->gz);
+  } else {
+    launch(k_batch_update_p<T>, eg, eb, st, m, bt->S, zp, p, x);
+    rc = launch_it_tiles<T>(s, 0, p, pro, EpiQB<T>{{q, p}, by}, st);
+    if (rc) return rc;
+    launch(k_batch_update_r_dots<T, PRE>, eg, eb, st, m, bt->S, q, r, d, z, bt->partials, bt->etickets, bt->etk0);
   }
-  hipLaunchKernelGGL(k_batch_update_p<T>, eg, dim3(kThreads), 0, st, m, static_cast<const PcgState*>(bt->S), zp, p, x);
-  rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(p), pro, EpiQB<T>{q, p, bt->S, bt->partials, bt->tickets, m}, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_batch_update_r_dots<T, PRE>), eg, dim3(kThreads), 0, st, m, bt->S, static_cast<const T*>(q), r,
-                     d, z, bt->partials, bt->etickets, static_cast<const int32_t*>(bt->etk0));
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -656,43 +513,30 @@ static int enqueue_batch_iteration_cg(lspcg_batch* bt, hipStream_t st) {
 template <typename T, bool SC>
 static int enqueue_batch_iteration_spai(lspcg_batch* bt, hipStream_t st) {
   lspcg_solver* s = bt->s;
-  T* x = static_cast<T*>(s->x);
-  T* r = static_cast<T*>(s->r);
-  T* z = static_cast<T*>(s->z);
-  T* t = static_cast<T*>(s->t);
-  T* p = static_cast<T*>(s->p);
-  T* q = static_cast<T*>(s->q);
+  T *x = as<T>(s->x), *r = as<T>(s->r), *z = as<T>(s->z), *t = as<T>(s->t), *p = as<T>(s->p), *q = as<T>(s->q);
   const BatchMap m = batch_map(bt);
   const ProTile pro{bt->S, m};
-  const dim3 eg(unsigned(bt->ntot / kThreads));
-  const T* d = SC ? static_cast<const T*>(s->d) : nullptr;
-  int rc = launch_it_tiles<T>(s, 2, static_cast<const T*>(r), pro, EpiT<T, SC>{t, d}, st);
+  const BySystem by{bt->S, bt->partials, bt->tickets, m};
+  const dim3 eg(unsigned(bt->ntot / kThreads)), eb(kThreads);
+  const T* d = SC ? as<T>(s->d) : nullptr;
+  const RowZ<T, SC> rowz{z, r, d, T(s->eps)};
+  int rc = launch_it_tiles<T>(s, 2, r, pro, EpiT<T, SC>{t, d}, st);
   if (rc) return rc;
   if (bt->sums) {
-    double* gz = bt->gz;
-    double* gq = bt->gq;
-    rc = launch_it_tiles<T>(s, 1, static_cast<const T*>(t), pro,
-                            EpiZG<T, SC>{z, r, d, T(s->eps), nullptr, nullptr, gz, 1}, st);
+    rc = launch_it_tiles<T>(s, 1, t, pro, EpiZG<T, SC>{rowz, {nullptr, nullptr, bt->gz, 1}}, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_batch_update_p_sums<T>, eg, dim3(kThreads), 0, st, m, bt->S, static_cast<const double*>(gz),
-                       static_cast<const T*>(z), p, x);
-    rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(p), pro, EpiQG<T>{q, p, nullptr, nullptr, gq, 1}, st);
+    launch(k_batch_update_p_sums<T>, eg, eb, st, m, bt->S, bt->gz, z, p, x);
+    rc = launch_it_tiles<T>(s, 0, p, pro, EpiQG<T>{{q, p}, {nullptr, nullptr, bt->gq, 1}}, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_batch_update_r_sums<T>, eg, dim3(kThreads), 0, st, m, bt->S, static_cast<const double*>(gz),
-                       static_cast<const double*>(gq), static_cast<const T*>(q), r);
-    LSPCG_HIP(hipGetLastError());
-    return LSPCG_OK;
+    launch(k_batch_update_r_sums<T>, eg, eb, st, m, bt->S, bt->gz, bt->gq, q, r);
+  } else {
+    rc = launch_it_tiles<T>(s, 1, t, pro, EpiZB<T, SC>{z, r, T(s->eps), bt->S, bt->partials, bt->tickets, m, d}, st);
+    if (rc) return rc;
+    launch(k_batch_update_p<T>, eg, eb, st, m, bt->S, z, p, x);
+    rc = launch_it_tiles<T>(s, 0, p, pro, EpiQB<T>{{q, p}, by}, st);
+    if (rc) return rc;
+    launch(k_batch_update_r<T>, eg, eb, st, m, bt->S, q, r);
   }
-  rc = launch_it_tiles<T>(s, 1, static_cast<const T*>(t), pro,
-                          EpiZB<T, SC>{z, r, T(s->eps), bt->S, bt->partials, bt->tickets, m, d}, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_batch_update_p<T>, eg, dim3(kThreads), 0, st, m, static_cast<const PcgState*>(bt->S),
-                     static_cast<const T*>(z), p, x);
-  rc = launch_it_tiles<T>(s, 0, static_cast<const T*>(p), pro, EpiQB<T>{q, p, bt->S, bt->partials, bt->tickets, m},
-                          st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_batch_update_r<T>, eg, dim3(kThreads), 0, st, m, static_cast<const PcgState*>(bt->S),
-                     static_cast<const T*>(q), r);
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -705,50 +549,6 @@ static int enqueue_batch_iteration(lspcg_batch* bt, hipStream_t st) {
     case LSPCG_PRECOND_EXT_SPAI_SCALED: return enqueue_batch_iteration_spai<T, true>(bt, st);
     default: return enqueue_batch_iteration_spai<T, false>(bt, st);
   }
-}
-
-// every system of the window in its own workgroup (k_pcg_small in batch mode): the whole loop in
-// one launch; rows per thread / threads from the window's largest system (launch_small's rule)
-template <typename T>
-static int launch_batch_small(lspcg_batch* bt, hipStream_t st) {
-  lspcg_solver* s = bt->s;
-  const bool spai = bt->precond == LSPCG_PRECOND_EXT_SPAI || bt->precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
-  const CsrView A = csr_view(s, 0, s->Av);
-  const CsrView L = spai ? csr_view(s, 1, s->Lv) : CsrView{};
-  const CsrView LT = spai ? csr_view(s, 2, s->LTv) : CsrView{};
-  auto* x = static_cast<T*>(s->x);
-  auto* r = static_cast<T*>(s->r);
-  auto* p = static_cast<T*>(s->p);
-  const T* d = static_cast<const T*>(s->d);
-  const int64_t n = bt->max_n;
-  const dim3 g(unsigned(bt->nsys));
-  const size_t lds = 3 * sizeof(T) * size_t(n);
-  auto go = [&](auto rows, auto threads) {
-    constexpr int R = decltype(rows)::value;
-    constexpr int TH = decltype(threads)::value;
-    const int32_t* boff = bt->boff;
-    const int32_t* bn = bt->bn;
-    switch (bt->precond) {  // d: of the block-diagonal system, 1 on padding rows (which no workgroup owns)
-      case LSPCG_PRECOND_NONE:
-        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_NONE, R, TH>), g, dim3(TH), lds, st, int32_t(n), bt->S, A, L,
-                           LT, d, x, r, p, boff, bn);
-        break;
-      case LSPCG_PRECOND_DIAGONAL:
-        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_DIAGONAL, R, TH>), g, dim3(TH), lds, st, int32_t(n), bt->S, A,
-                           L, LT, d, x, r, p, boff, bn);
-        break;
-      case LSPCG_PRECOND_EXT_SPAI_SCALED:
-        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_EXT_SPAI_SCALED, R, TH>), g, dim3(TH), lds, st, int32_t(n),
-                           bt->S, A, L, LT, d, x, r, p, boff, bn);
-        break;
-      default:
-        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_EXT_SPAI, R, TH>), g, dim3(TH), lds, st, int32_t(n), bt->S, A,
-                           L, LT, d, x, r, p, boff, bn);
-    }
-  };
-  dispatch_small(n, go);
-  LSPCG_HIP(hipGetLastError());
-  return LSPCG_OK;
 }
 
 // block-diagonal copy of M[0..nsys) with system k's block rows starting at brow[k] (padded)
@@ -765,11 +565,11 @@ static int cat_matrices(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* M, con
   int64_t e0 = 0;
   for (int k = 0; k < nsys; ++k) {
     const int64_t cnt = brow[k + 1] - brow[k] + (k == nsys - 1 ? 1 : 0);
-    hipLaunchKernelGGL(k_cat_rowptr, dim3(unsigned(std::min<int64_t>((cnt + 255) / 256, 1024))), dim3(256), 0, st, cnt,
-                       M[k]->nb, static_cast<const int32_t*>(M[k]->rowptr), int32_t(e0), C->rowptr + brow[k]);
+    launch(k_cat_rowptr, dim3(unsigned(std::min<int64_t>((cnt + 255) / 256, 1024))), dim3(256), st, cnt, M[k]->nb,
+           M[k]->rowptr, int32_t(e0), C->rowptr + brow[k]);
     if (M[k]->nnzb) {
-      hipLaunchKernelGGL(k_cat_colind, dim3(unsigned(std::min<int64_t>((M[k]->nnzb + 255) / 256, 1024))), dim3(256), 0,
-                         st, M[k]->nnzb, static_cast<const int32_t*>(M[k]->colind), int32_t(brow[k]), C->colind + e0);
+      launch(k_cat_colind, dim3(unsigned(std::min<int64_t>((M[k]->nnzb + 255) / 256, 1024))), dim3(256), st,
+             M[k]->nnzb, M[k]->colind, int32_t(brow[k]), C->colind + e0);
       LSPCG_HIP(hipMemcpyAsync(static_cast<char*>(C->vals) + vb * e0, M[k]->vals, vb * M[k]->nnzb,
                                hipMemcpyDeviceToDevice, st));
     }
@@ -928,15 +728,12 @@ int lspcg_batch_create_precond(lspcg_ctx* ctx, int nsys, const lspcg_mat* const*
     LSPCG_HIP(hipMemcpy(bt->bn, hn.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
   }
   if (needs_d) {  // d = diag of the block-diagonal system (solver_create / set_spai), 1 on padding rows
-    const dim3 eg{unsigned(netiles)};
-    if (bt->dtype == LSPCG_F64)
-      hipLaunchKernelGGL(k_batch_pad_d<double>, eg, dim3(kThreads), 0, ctx->stream, batch_map(bt.get()),
-                         static_cast<const int32_t*>(bt->boff), static_cast<const int32_t*>(bt->bn),
-                         static_cast<double*>(bt->s->d));
-    else
-      hipLaunchKernelGGL(k_batch_pad_d<float>, eg, dim3(kThreads), 0, ctx->stream, batch_map(bt.get()),
-                         static_cast<const int32_t*>(bt->boff), static_cast<const int32_t*>(bt->bn),
-                         static_cast<float*>(bt->s->d));
+    by_dtype(bt->dtype, [&](auto t) {
+      using T = decltype(t);
+      launch(k_batch_pad_d<T>, dim3(unsigned(netiles)), dim3(kThreads), ctx->stream, batch_map(bt.get()), bt->boff,
+             bt->bn, as<T>(bt->s->d));
+      return 0;
+    });
     LSPCG_HIP(hipGetLastError());
     LSPCG_HIP(hipStreamSynchronize(ctx->stream));
   }
@@ -962,14 +759,7 @@ int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, dou
     mi[k] = max_iter > 0 ? max_iter : bt->n[k];
     hoff[k + 1] = hoff[k] + ((res_hist && res_hist[k]) ? mi[k] + 2 : 0);
   }
-  if (hoff[ns] > bt->dhist_cap) {
-    LSPCG_HIP(hipStreamSynchronize(st));
-    (void)hipFree(bt->dhist);
-    bt->dhist = nullptr;
-    bt->dhist_cap = 0;
-    LSPCG_HIP(hipMalloc(&bt->dhist, sizeof(double) * hoff[ns]));
-    bt->dhist_cap = hoff[ns];
-  }
+  if (int rc = grow_hist(&bt->dhist, &bt->dhist_cap, hoff[ns], st)) return rc;
   std::unique_lock<std::mutex> sub(submit_mutex());  // as in lspcg_solver_solve
   LSPCG_HIP(hipEventRecord(s->ev_in, bt->ctx->stream));
   LSPCG_HIP(hipStreamWaitEvent(st, s->ev_in, 0));
@@ -983,30 +773,29 @@ int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, dou
   for (int k = 0; k < ns; ++k)
     bt->hS[k] = initial_state(rtol, s->eps, (res_hist && res_hist[k]) ? bt->dhist + hoff[k] : nullptr, mi[k]);
   LSPCG_HIP(hipMemcpyAsync(bt->S, bt->hS, sizeof(PcgState) * ns, hipMemcpyHostToDevice, st));
-  int rc = bt->dtype == LSPCG_F64 ? enqueue_batch_init<double>(bt, st) : enqueue_batch_init<float>(bt, st);
+  int rc = by_dtype(bt->dtype, [&](auto t) { return enqueue_batch_init<decltype(t)>(bt, st); });
   if (rc) return rc;
 
   // every system's state through the poll loop (small mode: one launch)
   StatePoll poll{ns, bt->S, bt->hS, {s->ev_poll, s->ev_poll2}, st, sub};
   std::vector<PcgState> cur(ns);
-  if (bt->small) {
-    rc = bt->dtype == LSPCG_F64 ? launch_batch_small<double>(bt, st) : launch_batch_small<float>(bt, st);
+  if (bt->small) {  // every system in its own workgroup: the whole loop in one launch
+    rc = by_dtype(bt->dtype, [&](auto t) {
+      return launch_pcg_small<decltype(t)>(bt->precond, ns, s, bt->max_n, bt->S, bt->boff, bt->bn, st);
+    });
     if (!rc) rc = poll.post();
     if (!rc) rc = poll.take(cur.data());
   } else {
-    auto one = [&] {
-      return bt->dtype == LSPCG_F64 ? enqueue_batch_iteration<double>(bt, st) : enqueue_batch_iteration<float>(bt, st);
-    };
+    auto one = [&] { return by_dtype(bt->dtype, [&](auto t) { return enqueue_batch_iteration<decltype(t)>(bt, st); }); };
     rc = poll.run(mi.data(), 32, [&](int c) { return bt->graphs.launch(st, c, one); }, cur.data());
   }
   if (rc) return rc;
-  const BatchMap m = batch_map(bt);
-  if (bt->dtype == LSPCG_F64)
-    hipLaunchKernelGGL(k_batch_x_fixup<double>, dim3(unsigned(bt->ntot / kThreads)), dim3(kThreads), 0, st, m, bt->S,
-                       static_cast<const double*>(s->p), static_cast<double*>(s->x));
-  else
-    hipLaunchKernelGGL(k_batch_x_fixup<float>, dim3(unsigned(bt->ntot / kThreads)), dim3(kThreads), 0, st, m, bt->S,
-                       static_cast<const float*>(s->p), static_cast<float*>(s->x));
+  by_dtype(bt->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_batch_x_fixup<T>, dim3(unsigned(bt->ntot / kThreads)), dim3(kThreads), st, batch_map(bt), bt->S,
+           as<T>(s->p), as<T>(s->x));
+    return 0;
+  });
   LSPCG_HIP(hipGetLastError());
   for (int k = 0; k < ns; ++k) {
     const char* src = (cur[k].bb == 0.0) ? cb : cx;  // scipy returns b when ‖b‖ = 0
@@ -1019,19 +808,7 @@ int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, dou
   float ms = 0.f;
   LSPCG_HIP(hipEventElapsedTime(&ms, s->ev_t0, s->ev_t1));
   if (t_solve_ms) *t_solve_ms = ms;
-  bool all = true;
-  for (int k = 0; k < ns; ++k) {
-    const PcgState& f = cur[k];
-    const SolveTail tail(f, mi[k]);
-    iters[k] = tail.iters;
-    status[k] = f.done == 1 ? LSPCG_OK : LSPCG_NOT_CONVERGED;
-    all = all && f.done == 1;
-    if (res_hist && res_hist[k]) {
-      LSPCG_HIP(hipMemcpy(res_hist[k], bt->dhist + hoff[k], sizeof(double) * tail.written, hipMemcpyDeviceToHost));
-      tail.nan_fill(res_hist[k]);
-    }
-  }
-  return all ? LSPCG_OK : LSPCG_NOT_CONVERGED;
+  return report_states(ns, cur.data(), mi.data(), bt->dhist, hoff.data(), iters, status, res_hist);
 }
 
 }  // extern "C"

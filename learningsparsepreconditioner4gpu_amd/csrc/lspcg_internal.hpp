@@ -219,7 +219,9 @@ __device__ __forceinline__ void block_reduce_dd(DD (&v)[N], DD* lds /* >= waves*
 // ---------------------------------------------------------------------------
 // Agent-scope helpers (MI355X_MICROARCH.md "Valid forms", table row 1): partials are
 // published with sc1 (atomic) stores, drained, then one relaxed ticket add; the last
-// arriver reads every partial with sc1 loads.
+// arriver reads every partial with sc1 loads.  Every last-arriver reduction (grid_reduce_dd,
+// grid_reduce_wide, grid_partial_groups, the batch's sys_reduce_tiles) goes through publish_dd /
+// read_dd, and the two-level ones through ticket_arrive.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void st_agent_f64(double* p, double v) {
   __hip_atomic_store(reinterpret_cast<unsigned long long*>(p),
@@ -232,6 +234,37 @@ __device__ __forceinline__ double ld_agent_f64(const double* p) {
   return __longlong_as_double(static_cast<long long>(u));
 }
 
+// Publish N DD partials at slot[0 .. 2N) (sc1 stores, drained: the ticket add that follows must not
+// pass them) / read one back in the last arriver.
+template <int N>
+__device__ __forceinline__ void publish_dd(double* slot, const DD (&v)[N]) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    st_agent_f64(slot + 2 * j + 0, v[j].s);
+    st_agent_f64(slot + 2 * j + 1, v[j].c);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+__device__ __forceinline__ DD read_dd(const double* slot) { return DD{ld_agent_f64(slot), ld_agent_f64(slot + 1)}; }
+
+// Arrival of arriver `idx` of `nt` on a two-level ticket, `top` its top line and the group lines
+// behind it: same-address device-scope atomics serialise at the memory side, so each group of
+// kTicketGroup arrivers counts on its own cache line and only the group's last arriver touches the
+// top line (<= nt/32 + 32 serialised atomics, not nt).  True in the last arriver of all, which
+// resets the top line when it is done with it (the group lines are reset here).
+__device__ __forceinline__ bool ticket_arrive(unsigned* top, unsigned idx, unsigned nt) {
+  const unsigned g = idx / kTicketGroup;
+  const unsigned gsize = min(unsigned(kTicketGroup), nt - g * kTicketGroup);
+  const unsigned ng = (nt + kTicketGroup - 1) / kTicketGroup;
+  unsigned* gt = top + size_t(kTicketStride) * (1 + g);
+  if (__hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gsize - 1) return false;
+  __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return __hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ng - 1;
+}
+__device__ __forceinline__ void ticket_reset(unsigned* top) {
+  __hip_atomic_store(top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Grid-wide deterministic reduction of N dot products.  Every workgroup of the launch
 // must call it exactly once (uniformly).  The workgroup that arrives last sums all
 // partials in block-index order and calls fin(values) on thread 0.
@@ -241,26 +274,8 @@ __device__ __forceinline__ void grid_reduce_dd(DD (&v)[N], double* partials, uns
   __shared__ int s_last;
   block_reduce_dd<N>(v, lds);
   if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      st_agent_f64(&partials[(size_t(blockIdx.x) * N + j) * 2 + 0], v[j].s);
-      st_agent_f64(&partials[(size_t(blockIdx.x) * N + j) * 2 + 1], v[j].c);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // two-level ticket: same-address device-scope atomics serialise at the memory side, so
-    // each group of kTicketGroup workgroups counts on its own cache line and only the group's
-    // last arriver touches the top-level ticket (<= G/32 + 32 serialised atomics, not G)
-    const unsigned G = gridDim.x;
-    const unsigned g = blockIdx.x / kTicketGroup;
-    const unsigned gsize = min(unsigned(kTicketGroup), G - g * kTicketGroup);
-    const unsigned ng = (G + kTicketGroup - 1) / kTicketGroup;
-    unsigned* gt = ticket + kTicketStride * (1 + g);
-    int last = 0;
-    if (__hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1) {
-      __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ng - 1;
-    }
-    s_last = last;
+    publish_dd<N>(&partials[size_t(blockIdx.x) * N * 2], v);
+    s_last = ticket_arrive(ticket, blockIdx.x, gridDim.x);
   }
   __syncthreads();
   if (!s_last) return;
@@ -273,22 +288,19 @@ __device__ __forceinline__ void grid_reduce_dd(DD (&v)[N], double* partials, uns
   for (int j = 0; j < N; ++j) acc[j] = dd_zero();
   const unsigned G = gridDim.x;
   for (unsigned base = 0; base < G; base += blockDim.x * PB) {
-    double ps[PB][N], pc[PB][N];
+    DD pv[PB][N];
 #pragma unroll
     for (int u = 0; u < PB; ++u) {
       unsigned b = base + threadIdx.x + u * blockDim.x;
       b = b < G ? b : G - 1;
 #pragma unroll
-      for (int j = 0; j < N; ++j) {
-        ps[u][j] = ld_agent_f64(&partials[(size_t(b) * N + j) * 2 + 0]);
-        pc[u][j] = ld_agent_f64(&partials[(size_t(b) * N + j) * 2 + 1]);
-      }
+      for (int j = 0; j < N; ++j) pv[u][j] = read_dd(&partials[(size_t(b) * N + j) * 2]);
     }
 #pragma unroll
     for (int u = 0; u < PB; ++u) {
       const bool ok = base + threadIdx.x + u * blockDim.x < G;
 #pragma unroll
-      for (int j = 0; j < N; ++j) acc[j] = dd_add(acc[j], DD{ok ? ps[u][j] : 0.0, ok ? pc[u][j] : 0.0});
+      for (int j = 0; j < N; ++j) acc[j] = dd_add(acc[j], DD{ok ? pv[u][j].s : 0.0, ok ? pv[u][j].c : 0.0});
     }
   }
   __syncthreads();
@@ -298,7 +310,87 @@ __device__ __forceinline__ void grid_reduce_dd(DD (&v)[N], double* partials, uns
 #pragma unroll
     for (int j = 0; j < N; ++j) out[j] = dd_value(acc[j]);
     fin(out);
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ticket_reset(ticket);
+  }
+}
+
+// one step of grid_reduce_wide's wave reduce-scatter (below), unrolled at compile time
+template <int HALF, int M, int N>
+__device__ __forceinline__ void wave_scatter_step(DD (&v)[N], int lane) {
+  if constexpr (HALF >= 1) {  // keep one half of the dots, hand the other to lane ^ M
+    const bool up = (lane & M) != 0;
+#pragma unroll
+    for (int j = 0; j < HALF; ++j) {
+      const DD keep = up ? v[j + HALF] : v[j];
+      const DD send = up ? v[j] : v[j + HALF];
+      v[j] = dd_add(keep, dd_shfl_xor(send, M));
+    }
+    wave_scatter_step<HALF / 2, M / 2>(v, lane);
+  } else if constexpr (M >= 1) {  // one dot left: the remaining distances
+    v[0] = dd_add(v[0], dd_shfl_xor(v[0], M));
+    wave_scatter_step<0, M / 2>(v, lane);
+  }
+}
+
+// grid_reduce_dd for the N = Kp or 2 Kp dots of a K-vector launch (N a power of two <= 16, 256
+// threads).  With one wave per SIMD on mid-size systems the reduction's dependent shuffles and
+// compensated adds are exposed, so the wave step is a reduce-scatter instead of N butterflies: at
+// xor distance 32, 16, ... each lane keeps one half of its dots and hands the other half to its
+// partner, until it holds ONE dot (dot lane * N / 64), which the remaining distances finish --
+// N - 1 + log2(64 / N) exchanges, not 6 N.  Every dot goes through the same tree whatever its index,
+// so a column's sums do not depend on where the column sits.  Threads j < N then add the four wave
+// totals of dot j, publish the workgroup's partial and take the two-level ticket as
+// grid_reduce_dd does; in the last arriver thread t sums dot t % N over blocks t / N, t / N + 256 / N,
+// ... (fixed order: the result does not depend on which workgroup came last), the lanes of equal
+// t % N are combined across the wave and the waves, and thread 0 runs fin(values).
+template <int N, class Fin>
+__device__ __forceinline__ void grid_reduce_wide(DD (&v)[N], double* partials, unsigned* ticket, Fin fin) {
+  static_assert(N >= 2 && N <= 16 && (N & (N - 1)) == 0, "2, 4, 8 or 16 dots");
+  constexpr int TH = kThreads, NW = TH / 64, NG = TH / N;
+  __shared__ DD lds[NW * N];
+  __shared__ double outv[N];
+  __shared__ int s_last;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  wave_scatter_step<N / 2, 32>(v, lane);
+  if ((lane & (64 / N - 1)) == 0) lds[wid * N + (lane * N >> 6)] = v[0];
+  __syncthreads();
+  if (tid < N) {
+    DD a = lds[tid];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) a = dd_add(a, lds[w * N + tid]);
+    const DD one[1] = {a};
+    publish_dd<1>(&partials[(size_t(blockIdx.x) * N + tid) * 2], one);
+  }
+  if (tid == 0) s_last = ticket_arrive(ticket, blockIdx.x, gridDim.x);
+  __syncthreads();
+  if (!s_last) return;
+  const unsigned G = gridDim.x;
+  const int j = tid & (N - 1);
+  DD acc = dd_zero();
+  for (unsigned b0 = unsigned(tid / N); b0 < G; b0 += 4 * NG) {
+    DD pv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) pv[u] = read_dd(&partials[(size_t(min(b0 + unsigned(u * NG), G - 1)) * N + j) * 2]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool ok = b0 + unsigned(u * NG) < G;
+      acc = dd_add(acc, DD{ok ? pv[u].s : 0.0, ok ? pv[u].c : 0.0});
+    }
+  }
+#pragma unroll
+  for (int mm = N; mm < 64; mm <<= 1) acc = dd_add(acc, dd_shfl_xor(acc, mm));  // lanes of equal dot
+  if (lane < N) lds[wid * N + lane] = acc;  // (the first phase's reads ended before the s_last barrier)
+  __syncthreads();
+  if (tid < N) {
+    DD a = lds[tid];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) a = dd_add(a, lds[w * N + tid]);
+    outv[tid] = dd_value(a);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    fin(outv);
+    ticket_reset(ticket);
   }
 }
 
@@ -347,12 +439,7 @@ __device__ __forceinline__ void grid_partial_groups(DD (&v)[N], double* partials
   const unsigned g0 = g * unsigned(gsz);
   const unsigned gn = min(unsigned(gsz), gridDim.x - g0);
   if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      st_agent_f64(&partials[(size_t(b) * N + j) * 2 + 0], v[j].s);
-      st_agent_f64(&partials[(size_t(b) * N + j) * 2 + 1], v[j].c);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    publish_dd<N>(&partials[size_t(b) * N * 2], v);
     unsigned* gt = ticket + kTicketStride * (1 + g);
     const int last = __hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gn - 1;
     if (last) __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -365,10 +452,8 @@ __device__ __forceinline__ void grid_partial_groups(DD (&v)[N], double* partials
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     const bool ok = lane < gn;
-    const size_t k = (size_t(g0 + (ok ? lane : 0)) * N + j) * 2;
-    const double s = ld_agent_f64(&partials[k + 0]);
-    const double c = ld_agent_f64(&partials[k + 1]);
-    a[j] = ok ? DD{s, c} : dd_zero();
+    const DD pv = read_dd(&partials[(size_t(g0 + (ok ? lane : 0)) * N + j) * 2]);
+    a[j] = ok ? pv : dd_zero();
   }
   wave_reduce_dd<N>(a);
   if (lane == 0) {

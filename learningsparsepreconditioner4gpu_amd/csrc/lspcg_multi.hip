@@ -11,7 +11,7 @@
 //   UP  per column: top-of-loop test ; x += α_{k-1} p_{k-1} ; p_k = p_{k-1}β + z
 //   KD  Q = A P ; per column π_k = p·q, α_k = ρ_k/π_k, iteration k+1     [SpMM A, Kp dots]
 //   UR  per column: r_{k+1} = r_k - α_k q
-// One last-arriver reduction per reducing launch (grid_reduce_wide) carries all columns' dots; its
+// One last-arriver reduction per reducing launch (grid_reduce_wide, lspcg_internal.hpp) carries all columns' dots; its
 // fin updates every running column's state.  A finished column is frozen: fin skips it, UP and UR keep its x, p and r (a
 // select per entry), and what KA / KB / KD compute in its lanes is never read.  Its deferred
 // x += α p is applied once, by the launch that unpacks X.  A workgroup leaves when every column is
@@ -43,103 +43,6 @@ struct ProAllDone {
   }
 };
 
-// one step of grid_reduce_wide's wave reduce-scatter (below), unrolled at compile time
-template <int HALF, int M, int N>
-__device__ __forceinline__ void wave_scatter_step(DD (&v)[N], int lane) {
-  if constexpr (HALF >= 1) {  // keep one half of the dots, hand the other to lane ^ M
-    const bool up = (lane & M) != 0;
-#pragma unroll
-    for (int j = 0; j < HALF; ++j) {
-      const DD keep = up ? v[j + HALF] : v[j];
-      const DD send = up ? v[j] : v[j + HALF];
-      v[j] = dd_add(keep, dd_shfl_xor(send, M));
-    }
-    wave_scatter_step<HALF / 2, M / 2>(v, lane);
-  } else if constexpr (M >= 1) {  // one dot left: the remaining distances
-    v[0] = dd_add(v[0], dd_shfl_xor(v[0], M));
-    wave_scatter_step<0, M / 2>(v, lane);
-  }
-}
-
-// grid_reduce_dd for the N = Kp or 2 Kp dots of a K-vector launch (N a power of two <= 16, 256
-// threads).  With one wave per SIMD on mid-size systems the reduction's dependent shuffles and
-// compensated adds are exposed, so the wave step is a reduce-scatter instead of N butterflies: at
-// xor distance 32, 16, ... each lane keeps one half of its dots and hands the other half to its
-// partner, until it holds ONE dot (dot lane * N / 64), which the remaining distances finish --
-// N - 1 + log2(64 / N) exchanges, not 6 N.  Every dot goes through the same tree whatever its index,
-// so a column's sums do not depend on where the column sits.  Threads j < N then add the four wave
-// totals of dot j, publish the workgroup's partial and take the two-level ticket as
-// grid_reduce_dd does; in the last arriver thread t sums dot t % N over blocks t / N, t / N + 256 / N,
-// ... (fixed order: the result does not depend on which workgroup came last), the lanes of equal
-// t % N are combined across the wave and the waves, and thread 0 runs fin(values).
-template <int N, class Fin>
-__device__ __forceinline__ void grid_reduce_wide(DD (&v)[N], double* partials, unsigned* ticket, Fin fin) {
-  static_assert(N >= 2 && N <= 16 && (N & (N - 1)) == 0, "2, 4, 8 or 16 dots");
-  constexpr int TH = kSellWG, NW = TH / 64, NG = TH / N;
-  __shared__ DD lds[NW * N];
-  __shared__ double outv[N];
-  __shared__ int s_last;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  wave_scatter_step<N / 2, 32>(v, lane);
-  if ((lane & (64 / N - 1)) == 0) lds[wid * N + (lane * N >> 6)] = v[0];
-  __syncthreads();
-  if (tid < N) {
-    DD a = lds[tid];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) a = dd_add(a, lds[w * N + tid]);
-    st_agent_f64(&partials[(size_t(blockIdx.x) * N + tid) * 2 + 0], a.s);
-    st_agent_f64(&partials[(size_t(blockIdx.x) * N + tid) * 2 + 1], a.c);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  if (tid == 0) {
-    const unsigned G = gridDim.x;
-    const unsigned g = blockIdx.x / kTicketGroup;
-    const unsigned gsize = min(unsigned(kTicketGroup), G - g * kTicketGroup);
-    const unsigned ng = (G + kTicketGroup - 1) / kTicketGroup;
-    unsigned* gt = ticket + kTicketStride * (1 + g);
-    int last = 0;
-    if (__hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1) {
-      __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ng - 1;
-    }
-    s_last = last;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  const unsigned G = gridDim.x;
-  const int j = tid & (N - 1);
-  DD acc = dd_zero();
-  for (unsigned b0 = unsigned(tid / N); b0 < G; b0 += 4 * NG) {
-    double ps[4], pc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const unsigned b = min(b0 + unsigned(u * NG), G - 1);
-      ps[u] = ld_agent_f64(&partials[(size_t(b) * N + j) * 2 + 0]);
-      pc[u] = ld_agent_f64(&partials[(size_t(b) * N + j) * 2 + 1]);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const bool ok = b0 + unsigned(u * NG) < G;
-      acc = dd_add(acc, DD{ok ? ps[u] : 0.0, ok ? pc[u] : 0.0});
-    }
-  }
-#pragma unroll
-  for (int mm = N; mm < 64; mm <<= 1) acc = dd_add(acc, dd_shfl_xor(acc, mm));  // lanes of equal dot
-  if (lane < N) lds[wid * N + lane] = acc;  // (the first phase's reads ended before the s_last barrier)
-  __syncthreads();
-  if (tid < N) {
-    DD a = lds[tid];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) a = dd_add(a, lds[w * N + tid]);
-    outv[tid] = dd_value(a);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    fin(outv);
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
 // KA: T = Lᵀ R (scaled: / d), EpiT per column
 template <typename T, int K, bool SCALED>
 struct EpiTK {
@@ -157,7 +60,7 @@ struct EpiTK {
   __device__ __forceinline__ void fin(const double*) const {}
 };
 
-// KB: Z = L T + ε R (scaled: + (ε R)/d); dots [2k] = ρ, [2k + 1] = ‖r‖² of column k; EpiZ::fin per
+// KB: Z = L T + ε R (scaled: + (ε R)/d); dots [2k] = ρ, [2k + 1] = ‖r‖² of column k; KB's keep per
 // running column
 template <typename T, int K, bool SCALED>
 struct EpiZK {
@@ -197,21 +100,12 @@ struct EpiZK {
 #pragma unroll
     for (int k = 0; k < K; ++k) done[k] = S[k].done, it[k] = S[k].iter, rho[k] = S[k].rho, hist[k] = S[k].hist;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      PcgState* St = S + k;
-      if (done[k]) continue;
-      St->rho_prev = rho[k];
-      St->rho = round_to<T>(v[2 * k]);
-      if (it[k] > 0) {
-        const double rr = round_to<T>(v[2 * k + 1]);
-        St->rr = rr;
-        if (hist[k]) hist[k][it[k]] = double(tsqrt<T>(T(rr)));
-      }
-    }
+    for (int k = 0; k < K; ++k)
+      if (!done[k]) keep_z<T>(S + k, it[k], rho[k], hist[k], v[2 * k], v[2 * k + 1]);
   }
 };
 
-// KD: Q = A P; dot [k] = π of column k; EpiQ<INC>::fin per running column
+// KD: Q = A P; dot [k] = π of column k; KC's keep and the count per running column
 template <typename T, int K>
 struct EpiQK {
   static constexpr int NDOT = K;
@@ -238,18 +132,12 @@ struct EpiQK {
 #pragma unroll
     for (int k = 0; k < K; ++k) done[k] = S[k].done, it[k] = S[k].iter, rho[k] = S[k].rho;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      PcgState* St = S + k;
-      if (done[k]) continue;
-      const double pq = round_to<T>(v[k]);
-      St->pq = pq;
-      St->alpha = double(T(rho[k]) / T(pq));
-      St->iter = it[k] + 1;
-    }
+    for (int k = 0; k < K; ++k)
+      if (!done[k]) keep_q<T, true>(S + k, it[k], rho[k], v[k]);
   }
 };
 
-// init: R_0 = B - A X0; dots [2k] = ‖r_0‖², [2k + 1] = ‖b‖² of column k; EpiResid::fin per column
+// init: R_0 = B - A X0; dots [2k] = ‖r_0‖², [2k + 1] = ‖b‖² of column k; the initial state per column
 // (a zero column -- the padding columns among them -- is done here)
 template <typename T, int K>
 struct EpiResidK {
@@ -280,26 +168,14 @@ struct EpiResidK {
 #pragma unroll
     for (int k = 0; k < K; ++k) rtol[k] = S[k].rtol, hist[k] = S[k].hist;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      PcgState* St = S + k;
-      const double rr = round_to<T>(v[2 * k]), bb = round_to<T>(v[2 * k + 1]);
-      const double bn = double(tsqrt<T>(T(bb)));
-      St->rr = rr;
-      St->bb = bb;
-      St->atol = fmax(0.0, rtol[k] * bn);
-      St->rho = rr;
-      St->alpha = 0.0;
-      St->iter = 0;
-      St->done = (bn == 0.0) ? 1 : 0;
-      if (hist[k]) hist[k][0] = double(tsqrt<T>(T(rr)));
-    }
+    for (int k = 0; k < K; ++k) init_state<T>(S + k, rtol[k], hist[k], v[2 * k], v[2 * k + 1], v[2 * k]);
   }
 };
 
 // UP over the interleaved vectors, 16-B vectors as k_update_p.  A lane's vectors j, j + stride, ...
 // all hold the same columns (the stride is a multiple of 256 vectors), so its per-entry scalars are
-// selected once, column by column (an indexed register array would go to scratch).  ProCheck per
-// column; workgroup 0's thread 0 writes the done codes.
+// selected once, column by column (an indexed register array would go to scratch).  The top-of-loop
+// test per column; workgroup 0's thread 0 writes the done codes.
 template <typename T, int K>
 __global__ void __launch_bounds__(kThreads) k_multi_update_p(int64_t nv, PcgState* S, const T* __restrict__ z,
                                                              T* __restrict__ p, T* __restrict__ x) {
@@ -325,14 +201,8 @@ __global__ void __launch_bounds__(kThreads) k_multi_update_p(int64_t nv, PcgStat
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     int code = 0;
-    if (!done[k]) {  // scipy's top-of-loop test (ProCheck)
-      if (it[k] >= mi[k]) {
-        code = 2;
-      } else {
-        const double rn = double(tsqrt<T>(T(rr[k])));
-        if (rn < atol[k]) code = 1;
-        else if (!(rn == rn) || rn == INFINITY) code = 3;
-      }
+    if (!done[k]) {
+      code = loop_test<T>(it[k], mi[k], rr[k], atol[k]);
       if (code && blockIdx.x == 0 && threadIdx.x == 0) S[k].done = code;
     }
     const bool live = !done[k] && !code;
@@ -631,14 +501,7 @@ int lspcg_solver_solve_multi(lspcg_solver* s, int nrhs, const void* B, void* X, 
   MultiWs* ws = s->multi;
   std::vector<int64_t> hoff(nrhs + 1, 0);
   for (int j = 0; j < nrhs; ++j) hoff[j + 1] = hoff[j] + ((res_hist && res_hist[j]) ? max_iter + 2 : 0);
-  if (hoff[nrhs] > ws->dhist_cap) {
-    LSPCG_HIP(hipStreamSynchronize(st));
-    (void)hipFree(ws->dhist);
-    ws->dhist = nullptr;
-    ws->dhist_cap = 0;
-    LSPCG_HIP(hipMalloc(&ws->dhist, sizeof(double) * hoff[nrhs]));
-    ws->dhist_cap = hoff[nrhs];
-  }
+  if (int rc = grow_hist(&ws->dhist, &ws->dhist_cap, hoff[nrhs], st)) return rc;
   void** v = ws->vec[kp_index(Kp)];
   const int pg = int(std::max<int64_t>(1, std::min<int64_t>((n * Kp + kThreads - 1) / kThreads, kElemBlocksMax)));
 
@@ -691,19 +554,7 @@ int lspcg_solver_solve_multi(lspcg_solver* s, int nrhs, const void* B, void* X, 
   float ms = 0.f;
   LSPCG_HIP(hipEventElapsedTime(&ms, s->ev_t0, s->ev_t1));
   if (t_solve_ms) *t_solve_ms = ms;
-  bool all = true;
-  for (int j = 0; j < nrhs; ++j) {
-    const PcgState& f = cur[j];
-    const SolveTail tail(f, max_iter);
-    iters[j] = tail.iters;
-    status[j] = f.done == 1 ? LSPCG_OK : LSPCG_NOT_CONVERGED;
-    all = all && f.done == 1;
-    if (res_hist && res_hist[j]) {
-      LSPCG_HIP(hipMemcpy(res_hist[j], ws->dhist + hoff[j], sizeof(double) * tail.written, hipMemcpyDeviceToHost));
-      tail.nan_fill(res_hist[j]);
-    }
-  }
-  return all ? LSPCG_OK : LSPCG_NOT_CONVERGED;
+  return report_states(nrhs, cur.data(), mi.data(), ws->dhist, hoff.data(), iters, status, res_hist);
 }
 
 }  // extern "C"

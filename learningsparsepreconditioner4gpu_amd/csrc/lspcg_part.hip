@@ -18,6 +18,7 @@
 #include <string>
 
 #include "lspcg_internal.hpp"
+#include "lspcg_pcg_kernels.hpp"
 #include "lspcg_sell.hpp"
 #include "lspcg_spmv.hpp"
 
@@ -45,7 +46,7 @@ struct EpiOwn {
 // group size from the launch's own grid: <= kPartGroups groups, the buffer zeroed beforehand
 __device__ __forceinline__ int part_gsz() { return int((gridDim.x + kPartGroups - 1) / kPartGroups); }
 
-// z = L t + ε r (EpiZ's expression); groups of r·z and r·r
+// z = L t + ε r (RowZ on the own rows); groups of r·z and r·r
 template <typename T>
 struct EpiZPart {
   static constexpr int NDOT = 2;
@@ -62,16 +63,12 @@ struct EpiZPart {
   __device__ __forceinline__ void prepare() { gsz = part_gsz(); }
   __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
     if (i < r0 || i >= n_own) return;
-    const T ri = gld(r + i);
-    const T zi = s + eps * ri;
-    gst(z + i, zi);
-    dd_fma(dots[0], double(ri), double(zi));
-    dd_fma(dots[1], double(ri), double(ri));
+    RowZ<T, false>{z, r, nullptr, eps}.row(i, s, dots);
   }
   __device__ __forceinline__ void fin(const double*) const {}
 };
 
-// q = A p; groups of p·q (EpiQG's expression)
+// q = A p (RowQ on the own rows); groups of p·q
 template <typename T>
 struct EpiQPart {
   static constexpr int NDOT = 1;
@@ -87,8 +84,7 @@ struct EpiQPart {
   __device__ __forceinline__ void prepare() { gsz = part_gsz(); }
   __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
     if (i < r0 || i >= n_own) return;
-    gst(q + i, s);
-    dd_fma(dots[0], double(gld(p + i)), double(s));
+    RowQ<T>{q, p}.row(i, s, dots);
   }
   __device__ __forceinline__ void fin(const double*) const {}
 };
@@ -146,7 +142,7 @@ struct PartState {
 };
 
 template <typename T>
-__device__ __forceinline__ T part_sqrt(T v) { return sqrt(v); }
+__device__ __forceinline__ T part_sqrt(T v) { return tsqrt<T>(v); }
 
 // total j of the gathered [world][64 groups][nd][2] pairs, rank-major (sum_groups' order)
 __device__ double part_total(const double* g, int world, int nd, int j) {
@@ -159,17 +155,10 @@ __device__ double part_total(const double* g, int world, int nd, int j) {
   return acc.s + acc.c;
 }
 
-// top-of-loop test (k_update_p_g's): sets done, returns true when the loop stops here
+// top-of-loop test (loop_test of lspcg_pcg_step.hpp): sets done, returns true when the loop stops here
 template <typename T>
 __device__ __forceinline__ bool part_test(PartState* S) {
-  int code = 0;
-  if (S->iter >= S->max_iter) {
-    code = 2;
-  } else {
-    const double rn = double(part_sqrt<T>(T(S->rr)));
-    if (rn < S->atol) code = 1;
-    else if (!(rn == rn) || rn == INFINITY) code = 3;
-  }
+  const int code = loop_test<T>(S->iter, S->max_iter, S->rr, S->atol);
   if (code) S->done = code;
   return code != 0;
 }

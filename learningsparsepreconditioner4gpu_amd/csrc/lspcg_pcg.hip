@@ -16,8 +16,9 @@
 // graph-captured chunks of iterations and polls once per chunk without changing the iteration
 // count or the iterate; the deferred x update of the last iteration is one fix-up launch.
 //
-// This unit: the single-system host code and the lspcg_solver_* ABI.  The loop's device code is
-// in lspcg_pcg_kernels.hpp, the parity dots in lspcg_pcg_parity.hpp, the solver handle and the host
+// This unit: the single-system host code and the lspcg_solver_* ABI.  scipy's scalar recurrence
+// (state, top-of-loop test, every transition) is in lspcg_pcg_step.hpp, the loop's device code in
+// lspcg_pcg_kernels.hpp, the parity dots in lspcg_pcg_parity.hpp, the solver handle and the host
 // control code shared with the batched solver (lspcg_batch.hip) in lspcg_solver.hpp.
 #include <hip/hip_runtime.h>
 
@@ -228,32 +229,26 @@ template <typename T, bool SC>
 static int enqueue_iteration_split(lspcg_solver* s, hipStream_t st) {
   const int64_t n = s->n;
   PcgState* S = s->S;
-  T* x = static_cast<T*>(s->x);
-  T* r = static_cast<T*>(s->r);
-  T* z = static_cast<T*>(s->z);
-  T* t = static_cast<T*>(s->t);
-  T* p = static_cast<T*>(s->p);
-  T* q = static_cast<T*>(s->q);
-  const T* d = static_cast<const T*>(s->d);
+  T *x = as<T>(s->x), *r = as<T>(s->r), *z = as<T>(s->z), *t = as<T>(s->t), *p = as<T>(s->p), *q = as<T>(s->q);
+  const T* d = as<T>(s->d);
   double* gz = s->groups;
   double* gq = s->groups + 4096 * 2 * 2;
-  const int eg = elem_vec_grid<T>(n);
+  const dim3 eg(elem_vec_grid<T>(n)), eb(kThreads);
   arm(s);
-  int rc = launch_it<T>(s, 2, static_cast<const T*>(r), ProDone{S}, EpiT<T, SC>{t, d}, st);
+  int rc = launch_it<T>(s, 2, r, ProDone{S}, EpiT<T, SC>{t, d}, st);
   if (rc) return rc;
   arm(s);
-  rc = launch_it<T>(s, 1, static_cast<const T*>(t), ProDone{S},
-                    EpiZG<T, SC>{z, r, d, T(s->eps), s->partials, s->ticket, gz, s->gsz_l}, st);
+  rc = launch_it<T>(s, 1, t, ProDone{S},
+                    EpiZG<T, SC>{{z, r, d, T(s->eps)}, {s->partials, s->ticket, gz, s->gsz_l}}, st);
   if (rc) return rc;
   arm(s);
-  LSPCG_LAUNCH_SPMV(k_update_p_g<T>, dim3(eg), dim3(kThreads), 0, st, n, S, static_cast<const double*>(gz), s->ng_l,
+  LSPCG_LAUNCH_SPMV(k_update_p_g<T>, eg, eb, 0, st, n, S, static_cast<const double*>(gz), s->ng_l,
                     static_cast<const T*>(z), p, x);
   arm(s);
-  rc = launch_it<T>(s, 0, static_cast<const T*>(p), ProDone{S}, EpiQG<T>{q, p, s->partials, s->ticket, gq, s->gsz_a},
-                    st);
+  rc = launch_it<T>(s, 0, p, ProDone{S}, EpiQG<T>{{q, p}, {s->partials, s->ticket, gq, s->gsz_a}}, st);
   if (rc) return rc;
   arm(s);
-  LSPCG_LAUNCH_SPMV(k_update_r_g<T>, dim3(eg), dim3(kThreads), 0, st, n, S, static_cast<const double*>(gq), s->ng_a,
+  LSPCG_LAUNCH_SPMV(k_update_r_g<T>, eg, eb, 0, st, n, S, static_cast<const double*>(gq), s->ng_a,
                     static_cast<const T*>(q), r);
   kernel_timer() = nullptr;
   LSPCG_HIP(hipGetLastError());
@@ -263,102 +258,79 @@ static int enqueue_iteration_split(lspcg_solver* s, hipStream_t st) {
 template <typename T>
 static int enqueue_iteration(lspcg_solver* s, hipStream_t st) {
   if (s->split)
-    return s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED ? enqueue_iteration_split<T, true>(s, st)
-                                                       : enqueue_iteration_split<T, false>(s, st);
+    return by_flag(s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED,
+                   [&](auto sc) { return enqueue_iteration_split<T, decltype(sc)::value>(s, st); });
   const int64_t n = s->n;
-  T* x = static_cast<T*>(s->x);
-  T* r = static_cast<T*>(s->r);
-  T* z = static_cast<T*>(s->z);
-  T* t = static_cast<T*>(s->t);
-  T* p = static_cast<T*>(s->p);
-  T* q = static_cast<T*>(s->q);
-  const T* d = static_cast<const T*>(s->d);
+  T *x = as<T>(s->x), *r = as<T>(s->r), *z = as<T>(s->z), *t = as<T>(s->t), *p = as<T>(s->p), *q = as<T>(s->q);
+  const T* d = as<T>(s->d);
   PcgState* S = s->S;
-  const int eg = elem_vec_grid<T>(n);
+  const ByLastArriver last{S, s->partials, s->ticket};
+  const dim3 eg(elem_vec_grid<T>(n)), eb(kThreads);
   int rc = LSPCG_OK;
   if (s->split_cg) {  // UP (ρ_k, ‖r_k‖² from UR's groups) -> KC (π groups) -> UR (+ next dots' groups)
     double* gz = s->groups;
     double* gq = s->groups + 4096 * 2 * 2;
     const bool jac = s->precond == LSPCG_PRECOND_DIAGONAL;
-    hipLaunchKernelGGL(k_update_p_g<T>, dim3(eg), dim3(kThreads), 0, st, n, S, static_cast<const double*>(gz), s->ng_r,
-                       static_cast<const T*>(jac ? z : r), p, x);
-    rc = launch_it<T>(s, 0, static_cast<const T*>(p), ProDone{S}, EpiQG<T>{q, p, s->partials, s->ticket, gq, s->gsz_a},
-                      st);
+    launch(k_update_p_g<T>, eg, eb, st, n, S, gz, s->ng_r, jac ? z : r, p, x);
+    rc = launch_it<T>(s, 0, p, ProDone{S}, EpiQG<T>{{q, p}, {s->partials, s->ticket, gq, s->gsz_a}}, st);
     if (rc) return rc;
     if (jac)
-      hipLaunchKernelGGL((k_update_r_gd<T, LSPCG_PRECOND_DIAGONAL>), dim3(eg), dim3(kThreads), 0, st, n, S,
-                         static_cast<const double*>(gq), s->ng_a, static_cast<const T*>(q), r, d, z, s->partials,
-                         s->ticket, s->gsz_r, gz);
+      launch(k_update_r_gd<T, LSPCG_PRECOND_DIAGONAL>, eg, eb, st, n, S, gq, s->ng_a, q, r, d, z, s->partials,
+             s->ticket, s->gsz_r, gz);
     else
-      hipLaunchKernelGGL((k_update_r_gd<T, LSPCG_PRECOND_NONE>), dim3(eg), dim3(kThreads), 0, st, n, S,
-                         static_cast<const double*>(gq), s->ng_a, static_cast<const T*>(q), r, d, z, s->partials,
-                         s->ticket, s->gsz_r, gz);
+      launch(k_update_r_gd<T, LSPCG_PRECOND_NONE>, eg, eb, st, n, S, gq, s->ng_a, q, r, d, z, s->partials, s->ticket,
+             s->gsz_r, gz);
     LSPCG_HIP(hipGetLastError());
     return LSPCG_OK;
   }
+  const bool spai = s->precond == LSPCG_PRECOND_EXT_SPAI || s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
+  const T* zp = z;  // what UP adds to p: z = M⁻¹ r, r itself without a preconditioner
   switch (s->precond) {
     case LSPCG_PRECOND_EXT_SPAI:
-    case LSPCG_PRECOND_EXT_SPAI_SCALED: {
-      const bool sc = s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
-      rc = sc ? launch_it<T>(s, 2, static_cast<const T*>(r), ProDone{S}, EpiT<T, true>{t, d}, st)
-              : launch_it<T>(s, 2, static_cast<const T*>(r), ProDone{S}, EpiT<T, false>{t, d}, st);
-      if (rc) return rc;
-      rc = sc ? launch_it<T>(s, 1, static_cast<const T*>(t), ProDone{S},
-                                   EpiZ<T, true>{z, r, d, T(s->eps), S, s->partials, s->ticket}, st)
-              : launch_it<T>(s, 1, static_cast<const T*>(t), ProDone{S},
-                                   EpiZ<T, false>{z, r, d, T(s->eps), S, s->partials, s->ticket}, st);
+    case LSPCG_PRECOND_EXT_SPAI_SCALED:
+      rc = by_flag(s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED, [&](auto scf) {
+        constexpr bool SC = decltype(scf)::value;
+        if (int r2 = launch_it<T>(s, 2, r, ProDone{S}, EpiT<T, SC>{t, d}, st)) return r2;
+        return launch_it<T>(s, 1, t, ProDone{S}, EpiZ<T, SC>{{z, r, d, T(s->eps)}, last}, st);
+      });
       if (rc) return rc;
       enqueue_ob<kObZ>(s, st, 2, r, z, r, r);
-      // top-of-loop test on ‖r_k‖ (reduced by KB) before the first update of iteration k
-      hipLaunchKernelGGL((k_update_p<T, ProCheck<T>>), dim3(eg), dim3(kThreads), 0, st, n, ProCheck<T>{S}, S,
-                         static_cast<const T*>(z), p, x);
       break;
-    }
-    case LSPCG_PRECOND_NONE:
-    case LSPCG_PRECOND_DIAGONAL:
-      hipLaunchKernelGGL((k_update_p<T, ProCheck<T>>), dim3(eg), dim3(kThreads), 0, st, n, ProCheck<T>{S}, S,
-                         static_cast<const T*>(s->precond == LSPCG_PRECOND_NONE ? r : z), p, x);
-      break;
+    case LSPCG_PRECOND_NONE: zp = r; break;
+    case LSPCG_PRECOND_DIAGONAL: break;
     case LSPCG_PRECOND_IC: {
-      // z = L⁻ᵀ L⁻¹ r (t holds L⁻¹ r), ρ = r·z; then the top-of-loop test in the p update
+      // z = L⁻ᵀ L⁻¹ r (t holds L⁻¹ r), ρ = r·z
       const int32_t* done = &S->done;
       if ((rc = enqueue_trsv(s->icL, s->planL, true, r, t, done, st))) return rc;
       if ((rc = enqueue_trsv(s->icU, s->planU, false, t, z, done, st))) return rc;
-      hipLaunchKernelGGL(k_dot_rho<T>, dim3(eg), dim3(kThreads), 0, st, n, S, static_cast<const T*>(r),
-                         static_cast<const T*>(z), s->partials, s->ticket);
+      launch(k_dot_rho<T>, eg, eb, st, n, S, r, z, s->partials, s->ticket);
       enqueue_ob<kObRho>(s, st, 1, r, z);
-      hipLaunchKernelGGL((k_update_p<T, ProCheck<T>>), dim3(eg), dim3(kThreads), 0, st, n, ProCheck<T>{S}, S,
-                         static_cast<const T*>(z), p, x);
       break;
     }
     default:
       set_error("unknown preconditioner");
       return LSPCG_ERR_ARG;
   }
-  const bool spai = s->precond == LSPCG_PRECOND_EXT_SPAI || s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
-  rc = spai ? launch_it<T>(s, 0, static_cast<const T*>(p), ProDone{S}, EpiQ<T, true>{q, p, S, s->partials, s->ticket},
-                           st)
-            : launch_it<T>(s, 0, static_cast<const T*>(p), ProDone{S}, EpiQ<T>{q, p, S, s->partials, s->ticket}, st);
+  // top-of-loop test on ‖r_k‖ (reduced by KB, the previous UR or the init) before the first update of
+  // iteration k
+  launch(k_update_p<T, ProCheck<T>>, eg, eb, st, n, ProCheck<T>{S}, S, zp, p, x);
+  rc = spai ? launch_it<T>(s, 0, p, ProDone{S}, EpiQ<T, true>{{q, p}, last}, st)
+            : launch_it<T>(s, 0, p, ProDone{S}, EpiQ<T>{{q, p}, last}, st);
   if (rc) return rc;
   enqueue_ob<kObQ>(s, st, 1, p, q);
   switch (s->precond) {
     case LSPCG_PRECOND_EXT_SPAI:
-    case LSPCG_PRECOND_EXT_SPAI_SCALED:
-      hipLaunchKernelGGL(k_update_r_nodot<T>, dim3(eg), dim3(kThreads), 0, st, n, S, static_cast<const T*>(q), r);
-      break;
+    case LSPCG_PRECOND_EXT_SPAI_SCALED: launch(k_update_r_nodot<T>, eg, eb, st, n, S, q, r); break;
     case LSPCG_PRECOND_NONE:
-      hipLaunchKernelGGL((k_update_r<T, LSPCG_PRECOND_NONE>), dim3(eg), dim3(kThreads), 0, st, n, S, q, r, d, z,
-                         s->partials, s->ticket);
+      launch(k_update_r<T, LSPCG_PRECOND_NONE>, eg, eb, st, n, S, q, r, d, z, s->partials, s->ticket);
       enqueue_ob<kObR>(s, st, 1, r, r);
       break;
     case LSPCG_PRECOND_DIAGONAL:
-      hipLaunchKernelGGL((k_update_r<T, LSPCG_PRECOND_DIAGONAL>), dim3(eg), dim3(kThreads), 0, st, n, S, q, r, d, z,
-                         s->partials, s->ticket);
+      launch(k_update_r<T, LSPCG_PRECOND_DIAGONAL>, eg, eb, st, n, S, q, r, d, z, s->partials, s->ticket);
       enqueue_ob<kObR, true>(s, st, 2, r, r, r, z);
       break;
     default:  // IC
-      hipLaunchKernelGGL((k_update_r<T, LSPCG_PRECOND_EXT_SPAI>), dim3(eg), dim3(kThreads), 0, st, n, S, q, r, d, z,
-                         s->partials, s->ticket);
+      launch(k_update_r<T, LSPCG_PRECOND_EXT_SPAI>, eg, eb, st, n, S, q, r, d, z, s->partials, s->ticket);
       enqueue_ob<kObRR>(s, st, 1, r, r);
   }
   LSPCG_HIP(hipGetLastError());
@@ -367,20 +339,14 @@ static int enqueue_iteration(lspcg_solver* s, hipStream_t st) {
 
 template <typename T>
 static int enqueue_init(lspcg_solver* s, hipStream_t st) {
-  T* r = static_cast<T*>(s->r);
-  const T* b = static_cast<const T*>(s->b);
-  const T* d = static_cast<const T*>(s->d);
-  T* z = static_cast<T*>(s->z);
-  const T* x = static_cast<const T*>(s->x);
+  T *r = as<T>(s->r), *z = as<T>(s->z);
+  const T *b = as<T>(s->b), *d = as<T>(s->d), *x = as<T>(s->x);
+  const ByLastArriver last{s->S, s->partials, s->ticket};
   const int rc = s->precond == LSPCG_PRECOND_DIAGONAL
-                     ? launch_it<T>(s, 0, x, ProNone{},
-                                          EpiResid<T, LSPCG_PRECOND_DIAGONAL>{r, b, d, z, s->S, s->partials, s->ticket},
-                                          st)
-                     : launch_it<T>(s, 0, x, ProNone{},
-                                          EpiResid<T, LSPCG_PRECOND_NONE>{r, b, d, z, s->S, s->partials, s->ticket},
-                                          st);
+                     ? launch_it<T>(s, 0, x, ProNone{}, EpiResid<T, LSPCG_PRECOND_DIAGONAL>{{r, b, d, z}, last}, st)
+                     : launch_it<T>(s, 0, x, ProNone{}, EpiResid<T, LSPCG_PRECOND_NONE>{{r, b, d, z}, last}, st);
   if (rc) return rc;
-  if (s->split_cg) hipLaunchKernelGGL(k_seed_groups, dim3(1), dim3(256), 0, st, s->S, s->groups, s->ng_r);
+  if (s->split_cg) launch(k_seed_groups, dim3(1), dim3(256), st, s->S, s->groups, s->ng_r);
   if (s->precond == LSPCG_PRECOND_DIAGONAL) enqueue_ob<kObInit, true>(s, st, 3, r, r, b, b, r, z);
   else enqueue_ob<kObInit>(s, st, 2, r, r, b, b);
   LSPCG_HIP(hipGetLastError());
@@ -389,8 +355,7 @@ static int enqueue_init(lspcg_solver* s, hipStream_t st) {
 
 template <typename T>
 static int enqueue_fixup(lspcg_solver* s, hipStream_t st) {
-  hipLaunchKernelGGL(k_x_fixup<T>, dim3(elem_grid(s->n)), dim3(kThreads), 0, st, s->n, s->S,
-                     static_cast<const T*>(s->p), static_cast<T*>(s->x));
+  launch(k_x_fixup<T>, dim3(elem_grid(s->n)), dim3(kThreads), st, s->n, s->S, as<T>(s->p), as<T>(s->x));
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -398,50 +363,10 @@ static int enqueue_fixup(lspcg_solver* s, hipStream_t st) {
 static bool small_path(const lspcg_solver* s) {
   if (s->dot_order != LSPCG_DOT_COMPENSATED) return false;  // parity mode: the multi-kernel schedule
   if (s->n <= 0 || s->n > s->small_n || s->precond == LSPCG_PRECOND_IC || s->Av.block_size != 1) return false;
-  if (s->n > int64_t(kSmallThreadsBig) * 3 || 3 * s->n * (s->dtype == LSPCG_F32 ? 4 : 8) > kSmallLds) return false;
+  if (s->n > int64_t(kSmallThreadsBig) * 3 || 3 * s->n * int64_t(esize(s->dtype)) > kSmallLds) return false;
   if (s->precond == LSPCG_PRECOND_EXT_SPAI || s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED)
     return s->Lv.block_size == 1 && s->LTv.block_size == 1;
   return true;
-}
-
-template <typename T>
-static int launch_small(lspcg_solver* s, hipStream_t st) {
-  const bool spai = s->precond == LSPCG_PRECOND_EXT_SPAI || s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
-  const CsrView A = csr_view(s, 0, s->Av);
-  const CsrView L = spai ? csr_view(s, 1, s->Lv) : CsrView{};
-  const CsrView LT = spai ? csr_view(s, 2, s->LTv) : CsrView{};
-  auto* x = static_cast<T*>(s->x);
-  auto* r = static_cast<T*>(s->r);
-  auto* p = static_cast<T*>(s->p);
-  const T* d = static_cast<const T*>(s->d);
-  const int32_t n = int32_t(s->n);
-  const dim3 g(1);
-  const size_t lds = 3 * sizeof(T) * size_t(n);
-  auto go = [&](auto rows, auto threads) {
-    constexpr int R = decltype(rows)::value;
-    constexpr int TH = decltype(threads)::value;
-    const dim3 b(TH);
-    switch (s->precond) {
-      case LSPCG_PRECOND_NONE:
-        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_NONE, R, TH>), g, b, lds, st, n, s->S, A, L, LT, d, x, r, p,
-                           nullptr, nullptr);
-        break;
-      case LSPCG_PRECOND_DIAGONAL:
-        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_DIAGONAL, R, TH>), g, b, lds, st, n, s->S, A, L, LT, d, x, r,
-                           p, nullptr, nullptr);
-        break;
-      case LSPCG_PRECOND_EXT_SPAI:
-        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_EXT_SPAI, R, TH>), g, b, lds, st, n, s->S, A, L, LT, d, x, r,
-                           p, nullptr, nullptr);
-        break;
-      default:
-        hipLaunchKernelGGL((k_pcg_small<T, LSPCG_PRECOND_EXT_SPAI_SCALED, R, TH>), g, b, lds, st, n, s->S, A, L, LT, d,
-                           x, r, p, nullptr, nullptr);
-    }
-  };
-  dispatch_small(n, go);
-  LSPCG_HIP(hipGetLastError());
-  return LSPCG_OK;
 }
 
 // diag(A) into s->d in the loop's numbering.  lspcg_mat_diagonal binary-searches sorted rows, so
@@ -791,7 +716,7 @@ int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int
   }
   *s->hS = initial_state(rtol, s->eps, dhist, max_iter);
   LSPCG_HIP(hipMemcpyAsync(s->S, s->hS, sizeof(PcgState), hipMemcpyHostToDevice, st));
-  int rc = s->dtype == LSPCG_F64 ? enqueue_init<double>(s, st) : enqueue_init<float>(s, st);
+  int rc = by_dtype(s->dtype, [&](auto t) { return enqueue_init<decltype(t)>(s, st); });
   if (rc) return rc;
 
   // graphs hold <= ~4096 nodes (IC: one launch per level of each triangular solve)
@@ -800,15 +725,17 @@ int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int
   StatePoll poll{1, s->S, s->hS, {s->ev_poll, s->ev_poll2}, st, sub};
   PcgState fin{};  // the state the loop ended in (later, early-exit launches leave it unchanged)
   if (small_path(s)) {  // one launch runs the whole loop (k_pcg_small)
-    rc = s->dtype == LSPCG_F64 ? launch_small<double>(s, st) : launch_small<float>(s, st);
+    rc = by_dtype(s->dtype, [&](auto t) {
+      return launch_pcg_small<decltype(t)>(s->precond, 1, s, n, s->S, nullptr, nullptr, st);
+    });
     if (!rc) rc = poll.post();
     if (!rc) rc = poll.take(&fin);
   } else {
-    auto one = [&] { return s->dtype == LSPCG_F64 ? enqueue_iteration<double>(s, st) : enqueue_iteration<float>(s, st); };
+    auto one = [&] { return by_dtype(s->dtype, [&](auto t) { return enqueue_iteration<decltype(t)>(s, st); }); };
     rc = poll.run(&max_iter, max_chunk, [&](int c) { return s->graphs.launch(st, c, one); }, &fin);
   }
   if (rc) return rc;
-  rc = s->dtype == LSPCG_F64 ? enqueue_fixup<double>(s, st) : enqueue_fixup<float>(s, st);
+  rc = by_dtype(s->dtype, [&](auto t) { return enqueue_fixup<decltype(t)>(s, st); });
   if (rc) return rc;
   const void* src = (fin.bb == 0.0) ? s->b : s->x;  // scipy returns b when ‖b‖ = 0
   if (n && s->ro.perm) {  // back to the caller's numbering
@@ -905,7 +832,7 @@ int lspcg_solver_time_kernels(lspcg_solver* s, const void* b, int64_t iters, dou
   LSPCG_HIP(hipMemsetAsync(s->x, 0, vb, st));
   *s->hS = initial_state(0.0, s->eps, nullptr, iters + 1);  // atol 0: no convergence stop, `iters` full iterations
   LSPCG_HIP(hipMemcpyAsync(s->S, s->hS, sizeof(PcgState), hipMemcpyHostToDevice, st));
-  int rc = s->dtype == LSPCG_F64 ? enqueue_init<double>(s, st) : enqueue_init<float>(s, st);
+  int rc = by_dtype(s->dtype, [&](auto t) { return enqueue_init<decltype(t)>(s, st); });
   if (rc) return rc;
   // each launch timed by its own start / end stamps (KernelTimer: the kernel durations rocprofv3's
   // trace reports, without the in-stream boundaries event pairs between launches would add)
@@ -919,7 +846,7 @@ int lspcg_solver_time_kernels(lspcg_solver* s, const void* b, int64_t iters, dou
   for (int64_t it = 0; it < iters && rc == LSPCG_OK; ++it) {
     s->tk = kt;
     s->tk_i = 0;
-    rc = s->dtype == LSPCG_F64 ? enqueue_iteration<double>(s, st) : enqueue_iteration<float>(s, st);
+    rc = by_dtype(s->dtype, [&](auto t) { return enqueue_iteration<decltype(t)>(s, st); });
     s->tk = nullptr;
     kernel_timer() = nullptr;
     if (rc) break;

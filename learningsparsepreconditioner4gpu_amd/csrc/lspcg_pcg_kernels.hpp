@@ -1,7 +1,9 @@
-// Device code of the PCG loop shared by the single-system solver (lspcg_pcg.hip) and the batched
-// lockstep solver (lspcg_batch.hip): the loop's state, the SpMV prologues / epilogues of every
-// phase, the update kernels and the one-workgroup solve -- templates only, so that either unit
-// instantiates what it launches.  Schedules: lspcg_pcg.hip's header and DESIGN.md §5.
+// Device code of the PCG loop shared by the single-system solver (lspcg_pcg.hip), the batched
+// lockstep solver (lspcg_batch.hip) and solve_multi (lspcg_multi.hip): the SpMV prologues, the row
+// bodies of every phase's epilogue and their compositions with a way of finishing the dots, the
+// update kernels and the one-workgroup solve -- templates only, so that each unit instantiates what
+// it launches.  The loop's state and scipy's scalar recurrence are in lspcg_pcg_step.hpp; every
+// kernel and epilogue here calls it.  Schedules: lspcg_pcg.hip's header and DESIGN.md §5.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,46 +12,19 @@
 #include <cstdint>
 
 #include "lspcg_internal.hpp"
+#include "lspcg_pcg_step.hpp"
 #include "lspcg_sell.hpp"
 #include "lspcg_spmv.hpp"
 
 namespace lspcg {
 
-struct PcgState {
-  double bb;        // ‖b‖²
-  double rr;        // ‖r_k‖² (rounded to T)
-  double rho;       // ρ_k = r_k·z_k (rounded to T)
-  double rho_prev;  // ρ_{k-1}
-  double pq;        // π_k = p_k·q_k (rounded to T)
-  double alpha;     // α_k = ρ_k/π_k computed in T
-  double atol;      // rtol·‖b‖
-  double rtol;
-  double eps;       // ε of ext_spai
-  double* hist;     // ‖r_k‖ history (nullable)
-  int64_t iter;     // completed iterations
-  int64_t max_iter;
-  int32_t done;     // 0 running, 1 converged, 2 max_iter reached, 3 non-finite residual
-  int32_t pad;
-  double rho_k;     // split schedule: ρ_k as UP summed it from KB's groups, read by UR (same bits)
-};
-
-template <typename T>
-__device__ __forceinline__ T tsqrt(T v) { return sqrt(v); }
-
-// Top-of-iteration test of scipy's loop: `for iteration in range(maxiter): if norm(r) < atol`.
+// the top-of-loop test as a launch's prologue (k_update_p of the last-arriver schedules)
 template <typename T>
 struct ProCheck {
   PcgState* S;
   __device__ __forceinline__ bool exit() const {
     if (S->done) return true;
-    int code = 0;
-    if (S->iter >= S->max_iter) {
-      code = 2;
-    } else {
-      const double rn = double(tsqrt<T>(T(S->rr)));
-      if (rn < S->atol) code = 1;
-      else if (!(rn == rn) || rn == INFINITY) code = 3;
-    }
+    const int code = loop_test<T>(S->iter, S->max_iter, S->rr, S->atol);
     if (code && blockIdx.x == 0 && threadIdx.x == 0) S->done = code;
     return code != 0;
   }
@@ -74,21 +49,46 @@ struct EpiT {
   __device__ __forceinline__ void fin(const double*) const {}
 };
 
+// ---- epilogues = a phase's row body x a way of finishing its dots ---------------------------
+// Row bodies (what a row's SpMV sum s becomes, and the row's terms of the phase's dots).  Where the
+// SELL kernels can load the row's own entry before its gathers, the body has prefetch() / row_pf()
+// (lspcg_sell.hpp; used where the composed epilogue sets PREFETCH).
+
+// init: r_0 = b - A x0 ; ‖r_0‖², ‖b‖² (+ z_0 = r_0/d, ρ_0 = r_0·z_0 for Jacobi)
+// (scipy: r = b - matvec(x) if x.any() else b.copy(); with x0 = 0 the subtraction returns b)
+template <typename T, int PRE>
+struct RowResid {
+  static constexpr int NDOT = PRE == LSPCG_PRECOND_DIAGONAL ? 3 : 2;
+  T* r;
+  const T* b;
+  const T* d;
+  T* z;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
+    const T bi = gld(b + i);
+    const T ri = bi - s;
+    gst(r + i, ri);
+    dd_fma(dots[0], double(ri), double(ri));
+    dd_fma(dots[1], double(bi), double(bi));
+    if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
+      const T zi = ri / gld(d + i);
+      gst(z + i, zi);
+      dd_fma(dots[2], double(ri), double(zi));
+    }
+  }
+};
+
 // KB: z = L t + ε r  (scaled: z = L t + (ε r)/d);  ρ = r·z and ‖r‖² in the same reduction
-// (the top-of-loop test on ‖r_k‖ then runs in the p update; r_0's norm comes from the init)
 template <typename T, bool SCALED>
-struct EpiZ {
+struct RowZ {
   static constexpr int NDOT = 2;
   T* z;
   const T* r;
   const T* d;
   T eps;
-  PcgState* S;
-  double* partials;
-  unsigned* ticket;
   __device__ __forceinline__ void prepare() {}
-  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    const T ri = gld(r + i);
+  __device__ __forceinline__ T prefetch(int64_t i) const { return gld(r + i); }
+  __device__ __forceinline__ void row_pf(int64_t i, T s, DD* dots, T ri) const {
     T zi;
     if constexpr (SCALED) zi = s + (eps * ri) / gld(d + i);
     else zi = s + eps * ri;
@@ -96,76 +96,83 @@ struct EpiZ {
     dd_fma(dots[0], double(ri), double(zi));
     dd_fma(dots[1], double(ri), double(ri));
   }
-  __device__ __forceinline__ void fin(const double* v) const {
-    S->rho_prev = S->rho;
-    S->rho = round_to<T>(v[0]);
-    const int64_t k = S->iter;
-    if (k > 0) {
-      const double rr = round_to<T>(v[1]);
-      S->rr = rr;
-      if (S->hist) S->hist[k] = double(tsqrt<T>(T(rr)));
-    }
-  }
+  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const { row_pf(i, s, dots, prefetch(i)); }
 };
 
-// KD: q = A p ; π = p·q ; α = ρ/π  (INC: this launch also completes the iteration -- ext_spai,
-// whose r update carries no reduction)
-template <typename T, bool INC = false>
-struct EpiQ {
+// KC / KD: q = A p ; π = p·q
+template <typename T>
+struct RowQ {
   static constexpr int NDOT = 1;
   T* q;
   const T* p;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ T prefetch(int64_t i) const { return gld(p + i); }
+  __device__ __forceinline__ void row_pf(int64_t i, T s, DD* dots, T pi) const {
+    gst(q + i, s);
+    dd_fma(dots[0], double(pi), double(s));
+  }
+  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const { row_pf(i, s, dots, prefetch(i)); }
+};
+
+// Finishing way 1: the launch's last arriver sums the workgroup partials (grid_reduce_dd) and runs
+// the composed epilogue's fin(values) on the state.
+struct ByLastArriver {
   PcgState* S;
   double* partials;
   unsigned* ticket;
-  __device__ __forceinline__ void prepare() {}
-  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    gst(q + i, s);
-    dd_fma(dots[0], double(gld(p + i)), double(s));
-  }
+};
+
+// Finishing way 2: the launch only pre-reduces per group of workgroups (grid_partial_groups); the
+// elementwise launches that consume the scalars sum the group totals -- the split schedules
+// (DESIGN.md "PCG schedule") and the batch's consumer-sum mode.  PF: the SELL kernels prefetch the
+// row's own entry (measured per phase: set for z when not scaled, and for q).
+struct ByGroups {
+  static constexpr bool GROUPS = true;
+  double* partials;
+  unsigned* ticket;
+  double* group_out;
+  int gsz;
+  __device__ __forceinline__ void fin(const double*) const {}
+};
+template <class Row, bool PF = false>
+struct EpiGroups : Row, ByGroups {
+  static constexpr bool PREFETCH = PF;
+};
+template <typename T, bool SCALED>
+using EpiZG = EpiGroups<RowZ<T, SCALED>, !SCALED>;
+template <typename T>
+using EpiQG = EpiGroups<RowQ<T>, true>;
+
+// (way 3, the batch's per-system last arrivers: lspcg_batch.hip)
+
+// KB of the last-arriver schedule (the top-of-loop test on ‖r_k‖ then runs in the p update;
+// r_0's norm comes from the init)
+template <typename T, bool SCALED>
+struct EpiZ : RowZ<T, SCALED>, ByLastArriver {
   __device__ __forceinline__ void fin(const double* v) const {
-    const double pq = round_to<T>(v[0]);
-    S->pq = pq;
-    S->alpha = double(T(S->rho) / T(pq));
-    if constexpr (INC) S->iter = S->iter + 1;
+    const int64_t k = S->iter;
+    const double rho_old = S->rho;
+    double* const hist = S->hist;
+    keep_z<T>(S, k, rho_old, hist, v[0], v[1]);
   }
 };
 
-// init: r_0 = b - A x0 ; ‖r_0‖², ‖b‖² (+ z_0 = r_0/d, ρ_0 = r_0·z_0 for Jacobi)
-// (scipy: r = b - matvec(x) if x.any() else b.copy(); with x0 = 0 the subtraction returns b)
-template <typename T, int PRE>
-struct EpiResid {
-  static constexpr int NDOT = PRE == LSPCG_PRECOND_DIAGONAL ? 3 : 2;
-  T* r;
-  const T* b;
-  const T* d;
-  T* z;
-  PcgState* S;
-  double* partials;
-  unsigned* ticket;
-  __device__ __forceinline__ void prepare() {}
-  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    const T bi = b[i];
-    const T ri = bi - s;
-    r[i] = ri;
-    dd_fma(dots[0], double(ri), double(ri));
-    dd_fma(dots[1], double(bi), double(bi));
-    if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
-      const T zi = ri / d[i];
-      z[i] = zi;
-      dd_fma(dots[2], double(ri), double(zi));
-    }
-  }
+// KD of the last-arriver schedule (INC: this launch also completes the iteration -- ext_spai,
+// whose r update carries no reduction)
+template <typename T, bool INC = false>
+struct EpiQ : RowQ<T>, ByLastArriver {
   __device__ __forceinline__ void fin(const double* v) const {
-    S->rr = round_to<T>(v[0]);
-    S->bb = round_to<T>(v[1]);
-    const double bn = double(tsqrt<T>(T(S->bb)));
-    S->atol = fmax(0.0, S->rtol * bn);
-    S->rho = PRE == LSPCG_PRECOND_DIAGONAL ? round_to<T>(v[2]) : S->rr;
-    S->alpha = 0.0;
-    S->iter = 0;
-    S->done = (bn == 0.0) ? 1 : 0;
-    if (S->hist) S->hist[0] = double(tsqrt<T>(T(S->rr)));
+    const int64_t k = INC ? S->iter : 0;
+    keep_q<T, INC>(S, k, S->rho, v[0]);
+  }
+};
+
+template <typename T, int PRE>
+struct EpiResid : RowResid<T, PRE>, ByLastArriver {
+  __device__ __forceinline__ void fin(const double* v) const {
+    const double rtol = S->rtol;
+    double* const hist = S->hist;
+    init_state<T>(S, rtol, hist, v[0], v[1], v[PRE == LSPCG_PRECOND_DIAGONAL ? 2 : 0]);
   }
 };
 
@@ -185,7 +192,7 @@ static int elem_vec_grid(int64_t n) {
 }
 
 // KC: x += α_{k-1} p_{k-1} (deferred, k > 0) ; p_k = p_{k-1}β + z (scipy `p *= beta; p += z`),
-// p_0 = z.  `Pro` = ProCheck for CG / Jacobi (top-of-loop test), ProDone for ext_spai.
+// p_0 = z.  `Pro` = ProCheck (the top-of-loop test) in every last-arriver schedule.
 template <typename T, typename Pro>
 __global__ void __launch_bounds__(kThreads) k_update_p(int64_t n, Pro pro, const PcgState* S,
                                                        const T* __restrict__ z, T* __restrict__ p,
@@ -225,6 +232,22 @@ __global__ void __launch_bounds__(kThreads) k_update_p(int64_t n, Pro pro, const
   }
 }
 
+// The per-row body of an r update that reduces: ri = r_{k+1}[i] (already stored) adds its term to
+// ‖r_{k+1}‖², Jacobi stores z = r/d and adds to ρ_{k+1} = r·z; BOTH: without a preconditioner ρ is
+// accumulated too (= r·r, for consumers that read the two sums side by side).
+template <typename T, int PRE, bool BOTH>
+__device__ __forceinline__ void r_dots_row(int64_t i, T ri, const T* __restrict__ d, T* __restrict__ z, DD& rr,
+                                           DD& rho) {
+  dd_fma(rr, double(ri), double(ri));
+  if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
+    const T zi = ri / d[i];
+    z[i] = zi;
+    dd_fma(rho, double(ri), double(zi));
+  } else if constexpr (BOTH) {
+    dd_fma(rho, double(ri), double(ri));
+  }
+}
+
 // KE: r -= α q ; ‖r‖² (+ Jacobi z = r/d, ρ = r·z) ; iteration count
 template <typename T, int PRE>
 __global__ void __launch_bounds__(kThreads) k_update_r(int64_t n, PcgState* S, const T* __restrict__ q,
@@ -240,14 +263,7 @@ __global__ void __launch_bounds__(kThreads) k_update_r(int64_t n, PcgState* S, c
   for (int j = 0; j < ND; ++j) dots[j] = dd_zero();
   const int64_t nv = n / W;
   const int64_t ts = int64_t(gridDim.x) * blockDim.x;
-  auto elem = [&](T ri, int64_t i) {
-    dd_fma(dots[0], double(ri), double(ri));
-    if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
-      const T zi = ri / d[i];
-      z[i] = zi;
-      dd_fma(dots[1], double(ri), double(zi));
-    }
-  };
+  auto elem = [&](T ri, int64_t i) { r_dots_row<T, PRE, false>(i, ri, d, z, dots[0], dots[ND - 1]); };
   for (int64_t j0 = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; j0 < nv; j0 += ts * kElemUnroll) {
     V rr[kElemUnroll], qq[kElemUnroll];
 #pragma unroll
@@ -275,15 +291,12 @@ __global__ void __launch_bounds__(kThreads) k_update_r(int64_t n, PcgState* S, c
     elem(ri, i);
   }
   grid_reduce_dd<ND>(dots, partials, ticket, [&](const double* v) {
-    const double rr2 = round_to<T>(v[0]);
-    S->rr = rr2;
-    if constexpr (PRE == LSPCG_PRECOND_NONE || PRE == LSPCG_PRECOND_DIAGONAL) {
-      S->rho_prev = S->rho;
-      S->rho = (PRE == LSPCG_PRECOND_DIAGONAL) ? round_to<T>(v[ND - 1]) : rr2;
-    }
+    constexpr bool RHO = PRE == LSPCG_PRECOND_NONE || PRE == LSPCG_PRECOND_DIAGONAL;  // IC: k_dot_rho
     const int64_t it = S->iter + 1;
+    const double rho_old = RHO ? S->rho : 0.0;
+    double* const hist = S->hist;
     S->iter = it;
-    if (S->hist) S->hist[it] = double(tsqrt<T>(T(rr2)));
+    keep_r<T, RHO>(S, it, rho_old, hist, v[0], v[ND - 1]);
   });
 }
 
@@ -326,70 +339,6 @@ __global__ void __launch_bounds__(kThreads) k_update_r_nodot(int64_t n, const Pc
 //   UR  α_k = ρ_k/π_k from GZ, GQ ; r_{k+1} = r_k - α_k q ; persists ρ_k, α_k, iteration k+1
 // Workgroup 0 of UP / UR is the only writer of the persistent state, which only later launches
 // read; every workgroup computes the same scalars (same group totals, same summation tree).
-struct GroupDots {
-  unsigned* ticket;
-  double* partials;
-  double* group_out;
-  int gsz;
-};
-
-template <typename T, bool SCALED>
-struct EpiZG {
-  static constexpr int NDOT = 2;
-  static constexpr bool GROUPS = true;
-  static constexpr bool PREFETCH = !SCALED;  // r[i] loaded before the row's gathers (SELL kernel)
-  T* z;
-  const T* r;
-  const T* d;
-  T eps;
-  double* partials;
-  unsigned* ticket;
-  double* group_out;
-  int gsz;
-  __device__ __forceinline__ void prepare() {}
-  __device__ __forceinline__ T prefetch(int64_t i) const { return gld(r + i); }
-  __device__ __forceinline__ void row_pf(int64_t i, T s, DD* dots, T ri) const {
-    const T zi = s + eps * ri;
-    gst(z + i, zi);
-    dd_fma(dots[0], double(ri), double(zi));
-    dd_fma(dots[1], double(ri), double(ri));
-  }
-  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    const T ri = gld(r + i);
-    T zi;
-    if constexpr (SCALED) zi = s + (eps * ri) / gld(d + i);
-    else zi = s + eps * ri;
-    gst(z + i, zi);
-    dd_fma(dots[0], double(ri), double(zi));
-    dd_fma(dots[1], double(ri), double(ri));
-  }
-  __device__ __forceinline__ void fin(const double*) const {}
-};
-
-template <typename T>
-struct EpiQG {
-  static constexpr int NDOT = 1;
-  static constexpr bool GROUPS = true;
-  static constexpr bool PREFETCH = true;  // p[i] loaded before the row's gathers (SELL kernel)
-  T* q;
-  const T* p;
-  double* partials;
-  unsigned* ticket;
-  double* group_out;
-  int gsz;
-  __device__ __forceinline__ void prepare() {}
-  __device__ __forceinline__ T prefetch(int64_t i) const { return gld(p + i); }
-  __device__ __forceinline__ void row_pf(int64_t i, T s, DD* dots, T pi) const {
-    gst(q + i, s);
-    dd_fma(dots[0], double(pi), double(s));
-  }
-  __device__ __forceinline__ void row(int64_t i, T s, DD* dots) const {
-    gst(q + i, s);
-    dd_fma(dots[0], double(gld(p + i)), double(s));
-  }
-  __device__ __forceinline__ void fin(const double*) const {}
-};
-
 // UP.  The first chunk's vector loads are issued before the group sums, so their latency overlaps
 // the scalar reduction instead of following it.  x is read and written with non-temporal accesses:
 // nothing else in the iteration touches it, and streaming it past the caches keeps its 8 B per row
@@ -431,19 +380,9 @@ __global__ void __launch_bounds__(kThreads) k_update_p_g(int64_t n, PcgState* S,
   if (done) return;
   const double rho = round_to<T>(v[0]);
   const double rr = k > 0 ? round_to<T>(v[1]) : rr0;  // ‖r_0‖² from the init launch
-  int code = 0;  // scipy's top-of-loop test (ProCheck)
-  if (k >= max_iter) {
-    code = 2;
-  } else {
-    const double rn = double(tsqrt<T>(T(rr)));
-    if (rn < atol) code = 1;
-    else if (!(rn == rn) || rn == INFINITY) code = 3;
-  }
+  const int code = loop_test<T>(k, max_iter, rr, atol);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (k > 0) {
-      S->rr = rr;
-      if (hist) hist[k] = double(tsqrt<T>(T(rr)));
-    }
+    keep_rr<T>(S, k, hist, rr);
     if (code) S->done = code;
     else S->rho_k = rho;
   }
@@ -501,13 +440,7 @@ __global__ void __launch_bounds__(kThreads) k_update_r_g(int64_t n, PcgState* S,
   if (done) return;
   const double pq = round_to<T>(vq[0]);
   const T alpha = T(rho) / T(pq);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    S->rho_prev = rho_prev;
-    S->rho = rho;
-    S->pq = pq;
-    S->alpha = double(alpha);
-    S->iter = k + 1;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) commit_step<T>(S, rho_prev, rho, pq, alpha, k + 1);
   for (int64_t j0 = jt; j0 < nv; j0 += ts * kElemUnroll) {
     if (j0 != jt) load(j0);
 #pragma unroll
@@ -555,24 +488,9 @@ __global__ void __launch_bounds__(kThreads) k_update_r_gd(int64_t n, PcgState* S
   if (done) return;  // uniform: UP exits too, nobody reads the groups
   const double pq = round_to<T>(vq[0]);
   const T alpha = T(rho) / T(pq);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    S->rho_prev = rho_prev;
-    S->rho = rho;
-    S->pq = pq;
-    S->alpha = double(alpha);
-    S->iter = k + 1;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) commit_step<T>(S, rho_prev, rho, pq, alpha, k + 1);
   DD dots[2] = {dd_zero(), dd_zero()};  // ρ_{k+1}, ‖r_{k+1}‖²
-  auto elem = [&](T ri, int64_t i) {
-    dd_fma(dots[1], double(ri), double(ri));
-    if constexpr (PRE == LSPCG_PRECOND_DIAGONAL) {
-      const T zi = ri / d[i];
-      z[i] = zi;
-      dd_fma(dots[0], double(ri), double(zi));
-    } else {
-      dd_fma(dots[0], double(ri), double(ri));
-    }
-  };
+  auto elem = [&](T ri, int64_t i) { r_dots_row<T, PRE, true>(i, ri, d, z, dots[1], dots[0]); };
   for (int64_t j0 = jt; j0 < nv; j0 += ts * kElemUnroll) {
     if (j0 != jt) load(j0);
 #pragma unroll
@@ -813,17 +731,8 @@ __global__ void __launch_bounds__(TH) k_pcg_small(int32_t n, PcgState* S, CsrVie
     double v2[2];
     small_dots<T, 2, TH>(dz, lds_z, v2);
     const double rr = k > 0 ? v2[1] : rr0;
-    if (k >= max_iter) {
-      code = 2;
-    } else {
-      const double rn = double(tsqrt<T>(T(rr)));
-      if (rn < atol) code = 1;
-      else if (!(rn == rn) || rn == INFINITY) code = 3;
-    }
-    if (tid == 0 && k > 0) {
-      S->rr = rr;
-      if (hist) hist[k] = double(tsqrt<T>(T(rr)));
-    }
+    code = loop_test<T>(k, max_iter, rr, atol);
+    if (tid == 0 && k > 0) keep_rr<T>(S, k, hist, rr);  // (one branch: k > 0 again inside folds away)
     if (code) break;
     rho_prev = rho;
     rho = v2[0];
@@ -863,11 +772,7 @@ __global__ void __launch_bounds__(TH) k_pcg_small(int32_t n, PcgState* S, CsrVie
     p[off + row[m]] = pr[m];
   }
   if (tid == 0) {
-    S->rho_prev = rho_prev;
-    S->rho = rho;
-    S->pq = pq;
-    S->alpha = double(alpha);
-    S->iter = k;
+    commit_step<T>(S, rho_prev, rho, pq, alpha, k);
     S->done = code;
   }
 }

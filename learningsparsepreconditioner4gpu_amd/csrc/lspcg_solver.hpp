@@ -1,7 +1,8 @@
 // The PCG solver handle and the host control code that the single-system solver (lspcg_pcg.hip)
 // and the batched lockstep solver (lspcg_batch.hip, which runs on a solver of the block-diagonal
-// system) share: the cache of captured iteration graphs, the poll loop, the one-workgroup
-// solve's dispatch, the initial state and the tail of a solve.
+// system) share, solve_multi (lspcg_multi.hip) too: the cache of captured iteration graphs, the
+// poll loop, the one-workgroup solve's launch, the initial state, the device history buffer and
+// the tail of a solve.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -204,6 +205,34 @@ void dispatch_small(int64_t n, F f) {
   else f(std::integral_constant<int, 3>{}, T1024{});
 }
 
+// k_pcg_small on `grid` systems of solver s's views: the one system of n rows (boff = bn = nullptr),
+// or a window's systems at rows boff[k] .. boff[k] + bn[k], the largest of n rows (d: 1 on a
+// window's padding rows, which no workgroup owns)
+template <typename T>
+int launch_pcg_small(int precond, int grid, lspcg_solver* s, int64_t n, PcgState* S, const int32_t* boff,
+                     const int32_t* bn, hipStream_t st) {
+  const bool spai = precond == LSPCG_PRECOND_EXT_SPAI || precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
+  const CsrView A = csr_view(s, 0, s->Av);
+  const CsrView L = spai ? csr_view(s, 1, s->Lv) : CsrView{};
+  const CsrView LT = spai ? csr_view(s, 2, s->LTv) : CsrView{};
+  const size_t lds = 3 * sizeof(T) * size_t(n);
+  dispatch_small(n, [&](auto rows, auto threads) {
+    auto go = [&](auto pre) {
+      constexpr int R = decltype(rows)::value, TH = decltype(threads)::value;
+      hipLaunchKernelGGL((k_pcg_small<T, decltype(pre)::value, R, TH>), dim3(unsigned(grid)), dim3(TH), lds, st,
+                         int32_t(n), S, A, L, LT, as<T>(s->d), as<T>(s->x), as<T>(s->r), as<T>(s->p), boff, bn);
+    };
+    switch (precond) {
+      case LSPCG_PRECOND_NONE: go(std::integral_constant<int, LSPCG_PRECOND_NONE>{}); break;
+      case LSPCG_PRECOND_DIAGONAL: go(std::integral_constant<int, LSPCG_PRECOND_DIAGONAL>{}); break;
+      case LSPCG_PRECOND_EXT_SPAI: go(std::integral_constant<int, LSPCG_PRECOND_EXT_SPAI>{}); break;
+      default: go(std::integral_constant<int, LSPCG_PRECOND_EXT_SPAI_SCALED>{});
+    }
+  });
+  LSPCG_HIP(hipGetLastError());
+  return LSPCG_OK;
+}
+
 // The state a solve starts from (the init launch adds the norms and atol).
 inline PcgState initial_state(double rtol, double eps, double* hist, int64_t max_iter) {
   PcgState init{};
@@ -221,6 +250,37 @@ struct SolveTail {
     for (int64_t k = written; k <= iters; ++k) hist[k] = NAN;
   }
 };
+
+// Device history buffer of at least `need` entries (grown after the stream has drained: a solve in
+// flight may write the old one)
+inline int grow_hist(double** buf, int64_t* cap, int64_t need, hipStream_t st) {
+  if (need <= *cap) return LSPCG_OK;
+  LSPCG_HIP(hipStreamSynchronize(st));
+  (void)hipFree(*buf);
+  *buf = nullptr;
+  *cap = 0;
+  LSPCG_HIP(hipMalloc(buf, sizeof(double) * need));
+  *cap = need;
+  return LSPCG_OK;
+}
+
+// iters / status / res_hist (nullable, entries nullable) of ns systems from their final states,
+// system k's history at dhist + hoff[k]; LSPCG_OK when every system converged
+inline int report_states(int ns, const PcgState* fin, const int64_t* max_iter, const double* dhist,
+                         const int64_t* hoff, int64_t* iters, int32_t* status, double* const* res_hist) {
+  bool all = true;
+  for (int k = 0; k < ns; ++k) {
+    const SolveTail tail(fin[k], max_iter[k]);
+    iters[k] = tail.iters;
+    status[k] = fin[k].done == 1 ? LSPCG_OK : LSPCG_NOT_CONVERGED;
+    all = all && fin[k].done == 1;
+    if (res_hist && res_hist[k]) {
+      LSPCG_HIP(hipMemcpy(res_hist[k], dhist + hoff[k], sizeof(double) * tail.written, hipMemcpyDeviceToHost));
+      tail.nan_fill(res_hist[k]);
+    }
+  }
+  return all ? LSPCG_OK : LSPCG_NOT_CONVERGED;
+}
 
 // The host's view of ns >= 1 device states while their loop runs: two pinned poll slots, each a
 // copy of all states plus an event, enqueued behind everything launched so far.
@@ -289,7 +349,7 @@ struct StatePoll {
       bool unknown = false, running = false;
       for (int k = 0; k < ns; ++k) {
         const PcgState& c = cur[k];
-        if (c.done) continue;  // ProCheck sets done (convergence, max_iter or a non-finite residual)
+        if (c.done) continue;  // the top-of-loop test sets done (convergence, max_iter or a non-finite residual)
         running = true;
         int64_t rk = -1;  // predicted iterations still needed after this state
         if (last_rr[k] > 0 && c.iter > last_it[k] && c.rr > 0 && c.rr < last_rr[k]) {

@@ -332,3 +332,46 @@ def test_infer_baseline_batched_matches_sequential(gpu_ctx, monkeypatch, heat_wi
     bat = run_baseline(samples, ws, method, rtol=1e-8, batch=8)
     assert calls and set(calls) == {method}
     _same_records(seq, bat, len(samples))
+
+
+@pytest.fixture(scope="module")
+def nonfinite_window():
+    """An ordinary system, one whose alpha is not finite after iteration 0 (diag(+1, -1, ...), L = I,
+    b = 1: p.Ap is exactly 0) and one whose right-hand side holds an inf (stops at k = 0), with each
+    system's single solve per kind (max_iter 20), computed on first use."""
+    As = [sp.csr_matrix(P.poisson2d_grid(24, 20)[0]),
+          sp.diags(np.where(np.arange(600) % 2 == 0, 1.0, -1.0)).tocsr(),
+          sp.csr_matrix(P.poisson2d_grid(40, 33)[0])]
+    Ls = [_cases.spai_like(As[0], seed=0), sp.identity(600, format="csr"), _cases.spai_like(As[2], seed=2)]
+    bs_ = [As[0] @ np.ones(As[0].shape[0]), np.ones(600), As[2] @ np.ones(As[2].shape[0])]
+    bs_[2][5] = np.inf
+    cache = {}
+
+    def single(kind):
+        if kind not in cache:
+            cache[kind] = [_single(A, L, b, kind, 1e-8, max_iter=20, eps=1e-3) for A, L, b in zip(As, Ls, bs_)]
+        return cache[kind]
+
+    return As, Ls, bs_, single
+
+
+@pytest.mark.parametrize("mode", ["last_arriver", "consumer_sums", "one_workgroup"])
+@pytest.mark.parametrize("kind", ("none", "diagonal", "ext_spai", "ext_spai_scaled"))
+def test_nonfinite_system_stops_alone(gpu_ctx, monkeypatch, nonfinite_window, kind, mode):
+    """The non-finite stop (done == 3) in both lockstep reduction modes and in the window of
+    one-workgroup solves: every system reports what its single solve reports (count, verdict,
+    NaN-filled history), and the ordinary system beside the two stopped ones is not disturbed."""
+    monkeypatch.delenv("LSPCG_BATCH_REDUCE", raising=False)
+    if mode == "one_workgroup":
+        monkeypatch.setenv("LSPCG_BATCH_SMALL", "1")
+    else:
+        monkeypatch.setenv("LSPCG_BATCH_SMALL", "0")
+        monkeypatch.setenv("LSPCG_BATCH_REDUCE", "0" if mode == "last_arriver" else "1")
+    As, Ls, bs_, single = nonfinite_window
+    res, xs = _solve(_make(As, Ls, kind, eps=1e-3), bs_, 1e-8, max_iter=20)
+    for k, ((it, conv, h), (it1, conv1, x1, h1)) in enumerate(zip(res, single(kind))):
+        print(f"{kind} {mode} system {k}: batch {it} {conv} {h[:2]}, single {it1} {conv1} {h1[:2]}")
+        assert (it, conv) == (it1, conv1), (k, it, it1)
+        np.testing.assert_array_equal(h, h1)  # NaN and inf entries compare equal
+    assert [r[:2] for r in res[1:]] == [(20, False), (20, False)]
+    assert _rel(xs[0], single(kind)[0][2]) <= 1e-12

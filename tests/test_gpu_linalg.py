@@ -387,3 +387,58 @@ def test_new_spai_on_the_same_solver_equals_a_fresh_solver(gpu_ctx, monkeypatch,
         del f
         for g in (got, got2):
             assert g[0] == want[0] and np.array_equal(g[1], want[1]) and np.array_equal(g[2], want[2]), (case, eps)
+
+
+# ---- the non-finite stop (done == 3) through every schedule of the single solver -------------
+_NF_SCHEDULES = {"default": {}, "last_arriver": {"LSPCG_SPLIT_REDUCE": "0"}, "csr_views": {"LSPCG_NO_SELL": "1"},
+                 "one_workgroup": {}}
+
+
+def _nonfinite_system(which, small):
+    """(A, L, b): (a) diag(+1, -1, ...) with L = I and b = 1 -- p.Ap is exactly 0, so alpha is not
+    finite after iteration 0 and the stop comes at k = 1; (b) Poisson with an inf entry in b -- the
+    stop comes at k = 0.  small: the size the one-workgroup solve takes (n <= 2560)."""
+    if which == "a":
+        n = 1320 if small else 4096
+        A = sp.diags(np.where(np.arange(n) % 2 == 0, 1.0, -1.0)).tocsr()
+        return A, sp.identity(n, format="csr"), np.ones(n)
+    A = sp.csr_matrix(P.poisson2d_grid(*((40, 33) if small else (64, 64)))[0])
+    b = A @ np.ones(A.shape[0])
+    b[5] = np.inf
+    return A, _cases.spai_like(A), b
+
+
+@pytest.mark.parametrize("schedule", list(_NF_SCHEDULES))
+@pytest.mark.parametrize("which", ["a", "b"])
+@pytest.mark.parametrize("method", ["none", "diagonal", "ext_spai", "ext_spai_scaled"])
+def test_nonfinite_residual_stops_every_schedule(gpu_ctx, monkeypatch, method, which, schedule):
+    """A residual that is not finite stops the loop (done == 3) with the same report from every
+    schedule: max_iter iterations, not converged, max_iter + 1 history entries of which only those
+    before the stop can be finite, and for a stop at k = 0 the iterate as it was passed in.  The
+    count is the oracle's, which runs scipy's loop to max_iter."""
+    from learningsparsepreconditioner4gpu_amd.linalg import PreconditionedConjugateGradient
+
+    for k in ("LSPCG_SPLIT_REDUCE", "LSPCG_NO_SELL", "LSPCG_SMALL_N"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in _NF_SCHEDULES[schedule].items():
+        monkeypatch.setenv(k, v)
+    A, L, b = _nonfinite_system(which, small=schedule == "one_workgroup")
+    eps = 1e-3
+    s = PreconditionedConjugateGradient(A, device="cuda", preconditioner=method)
+    if method.startswith("ext_spai"):
+        s.set_spai(L, eps)
+    bt = torch.from_numpy(b).cuda()
+    x = torch.zeros_like(bt)
+    it, conv, _, h = s.solve(bt, x, rtol=1e-8, max_iter=20, return_history=True)
+    print(f"{method} ({which}) {schedule}: iters {it} converged {conv} history {h[:3]} ... ({len(h)} entries)")
+    with np.errstate(all="ignore"):
+        it_o = O.pcg(A, b, _oracle_psolve(method, A, L, eps), rtol=1e-8, max_iter=20, dot="exact")[0]
+    assert it == it_o == 20 and not conv
+    assert len(h) == 21
+    if which == "a":
+        if method == "none":
+            assert h[0] == np.sqrt(A.shape[0])
+        assert np.isfinite(h[0]) and not np.isfinite(h[1:]).any()
+    else:
+        assert not np.isfinite(h).any()
+        assert not x.cpu().numpy().any()
