@@ -5,7 +5,7 @@
 // EpiT / RowZ's divisions by d = diag(A)); no preconditioner and the diagonal one have no KA / KB
 // and run three (UP, KC, UR), UR also reducing the next iteration's dots (‖r‖², ρ = r·z) per
 // system.  In every launch
-//   * one row tile per workgroup (launch_spmv_sell_cfg one_tile_per_wg), so a workgroup's dot
+//   * one row tile per workgroup (launch_sell one_tile_per_wg), so a workgroup's dot
 //     partial is its tile's and its prologue tests the tile's own system (done systems' tiles
 //     leave at once);
 //   * per-system last-arriver dot reductions (batch_sys_reduce): the last tile of a system to
@@ -451,13 +451,9 @@ static int launch_it_tiles(lspcg_solver* s, int w, const T* x, Pro pro, Epi epi,
   const SellPattern* P = s->sp[w];
   if (!P) return LSPCG_ERR_UNSUPPORTED;
   if constexpr (sizeof(T) == 8) {
-    if (s->svd[w] == LSPCG_F32) {
-      launch_spmv_sell_cfg<T, float>(*P, s->sv[w], GatherVec<T>{x}, pro, epi, st, true);
-      return LSPCG_OK;
-    }
+    if (s->svd[w] == LSPCG_F32) return launch_sell<T, float>(*P, s->sv[w], GatherVec<T>{x}, pro, epi, st, true);
   }
-  launch_spmv_sell_cfg<T, T>(*P, s->sv[w], GatherVec<T>{x}, pro, epi, st, true);
-  return LSPCG_OK;
+  return launch_sell<T, T>(*P, s->sv[w], GatherVec<T>{x}, pro, epi, st, true);
 }
 
 template <typename T>

@@ -547,10 +547,10 @@ int lspcg_spmv(lspcg_ctx* ctx, const lspcg_mat* A, const void* x, void* y) {
     const int32_t* pm = c->ro.perm;
     int rc = vec_permute(A->dtype, nb, A->block_size, pm, x, c->xs, false, ctx->stream);
     if (!rc)
-      by_dtype_bs(A->dtype, A->block_size, [&](auto t, auto bs) {
+      rc = by_dtype_bs(A->dtype, A->block_size, [&](auto t, auto bs) {
         using T = decltype(t);
-        launch_spmv_sell_cfg<T, T>(c->P, c->vals, GatherVec<T>{as<T>(c->xs)}, ProNone{},
-                                   EpiStorePerm<T, decltype(bs)::value>{as<T>(y), pm}, ctx->stream);
+        return launch_sell<T, T>(c->P, c->vals, GatherVec<T>{as<T>(c->xs)}, ProNone{},
+                                 EpiStorePerm<T, decltype(bs)::value>{as<T>(y), pm}, ctx->stream);
       });
     kernel_timer() = kt;
     if (rc) return rc;
@@ -560,10 +560,8 @@ int lspcg_spmv(lspcg_ctx* ctx, const lspcg_mat* A, const void* x, void* y) {
   const int rc = by_dtype(A->dtype, [&](auto t) -> int {
     using T = decltype(t);
     const EpiStore<T> epi{as<T>(y)};
-    if (const SellCopy* c = A->sell) {
-      launch_spmv_sell_cfg<T, T>(c->P, c->vals, GatherVec<T>{as<T>(x)}, ProNone{}, epi, ctx->stream);
-      return LSPCG_OK;
-    }
+    if (const SellCopy* c = A->sell)
+      return launch_sell<T, T>(c->P, c->vals, GatherVec<T>{as<T>(x)}, ProNone{}, epi, ctx->stream);
     return launch_spmv_any<T>(A, as<T>(x), ProNone{}, epi, ctx->stream);
   });
   if (rc) return rc;
@@ -714,13 +712,15 @@ int lspcg_spmv_sell_timed(lspcg_ctx* ctx, const lspcg_mat* A, int compact, const
     const GatherPairDiag gp{x2, 0.0};
     const EpiStore<double> epi{static_cast<double*>(y)};
     rc = spmv_timed_impl(ctx, A, reps, flush_bytes, avg_ms, [&]() -> int {
+      int lrc;
       if (compact & 4) {
-        if (compact & 1) launch_spmv_sell_cfg<double, float>(P, v, gp, ProNone{}, epi, st);
-        else launch_spmv_sell_cfg<double, double>(P, v, gp, ProNone{}, epi, st);
+        lrc = (compact & 1) ? launch_sell<double, float>(P, v, gp, ProNone{}, epi, st)
+                            : launch_sell<double, double>(P, v, gp, ProNone{}, epi, st);
       } else {
-        if (compact & 1) launch_spmv_sell_cfg<double, float>(P, v, gx, ProNone{}, epi, st);
-        else launch_spmv_sell_cfg<double, double>(P, v, gx, ProNone{}, epi, st);
+        lrc = (compact & 1) ? launch_sell<double, float>(P, v, gx, ProNone{}, epi, st)
+                            : launch_sell<double, double>(P, v, gx, ProNone{}, epi, st);
       }
+      if (lrc) return lrc;
       LSPCG_HIP(hipGetLastError());
       return LSPCG_OK;
     });

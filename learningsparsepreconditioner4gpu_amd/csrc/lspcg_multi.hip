@@ -49,6 +49,7 @@ struct EpiTK {
   static constexpr int NDOT = 0;
   T* t;
   const T* d;
+  __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void row(int64_t i, const T (&s)[K], DD*) const {
     T o[K];
     T di = T(1);
@@ -73,6 +74,7 @@ struct EpiZK {
   PcgState* S;
   double* partials;
   unsigned* ticket;
+  __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void row(int64_t i, const T (&s)[K], DD* dots) const {
     T ri[K], zi[K];
     RowK<T, K>::load(r + i * K, ri);
@@ -115,6 +117,7 @@ struct EpiQK {
   PcgState* S;
   double* partials;
   unsigned* ticket;
+  __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void row(int64_t i, const T (&s)[K], DD* dots) const {
     T pi[K];
     RowK<T, K>::load(p + i * K, pi);
@@ -148,6 +151,7 @@ struct EpiResidK {
   PcgState* S;
   double* partials;
   unsigned* ticket;
+  __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void row(int64_t i, const T (&s)[K], DD* dots) const {
     T bi[K], ri[K];
     RowK<T, K>::load(b + i * K, bi);
@@ -403,13 +407,9 @@ static int multi_workspace(lspcg_solver* s, int Kp) {
 template <typename T, int K, class Pro, class Epi>
 static int launch_spmm(lspcg_solver* s, int w, const T* x, Pro pro, Epi epi, hipStream_t st) {
   const SellPattern* P = s->sp[w];
-  bool ok = false;
-  if (P) {
-    if (sizeof(T) == 8 && s->svd[w] == LSPCG_F32) ok = launch_spmm_cfg<T, float, K>(*P, s->sv[w], x, pro, epi, st);
-    else ok = launch_spmm_cfg<T, T, K>(*P, s->sv[w], x, pro, epi, st);
-  }
-  LSPCG_CHECK(ok, LSPCG_ERR_UNSUPPORTED, "solve_multi: view without a K-vector kernel");
-  return LSPCG_OK;
+  LSPCG_CHECK(P && spmm_supported(*P), LSPCG_ERR_UNSUPPORTED, "solve_multi: view without a K-vector kernel");
+  if (sizeof(T) == 8 && s->svd[w] == LSPCG_F32) return launch_sell<T, float, K>(*P, s->sv[w], GatherVec<T>{x}, pro, epi, st);
+  return launch_sell<T, T, K>(*P, s->sv[w], GatherVec<T>{x}, pro, epi, st);
 }
 
 template <typename T, int K>

@@ -11,6 +11,15 @@
 // and is accumulated in the row's index order -- scipy's csr_matvec order, so results are
 // bit-identical to the CSR kernels.  Padding slots (k >= row length) are skipped by a
 // predicate, never added (0*inf and -0.0 + 0.0 must not leak into the sum).
+//
+// What is here: the layouts' constants and SellPattern; one kernel per layout -- k_spmv_sell
+// (SELL-64, SELL-64C), k_spmv_sellj (SELL-64J / SELL-64X), k_spmv_bsell3 (BSELL-64), k_spmv_sdia
+// (SELL-DIA), k_spmv_bsdia3 (BSELL-DIA); for solve_multi's K = 2, 4, 8 interleaved vectors
+// k_spmv_sell takes K as its last template parameter and SELL-DIA has k_spmm_sdia -- over shared
+// pieces: the column-word decode (sell_word / sell_decode), the SELL-DIA slice metadata
+// (SdiaSlice), the gather of one or K vectors (gather_k) and the row hand-off to the epilogue
+// (RowOut); and ONE launch function, launch_sell (grid rule, minimum-workgroups rule, argument
+// builders, dispatch over the layout), which fails loudly where a layout has no kernel.
 #pragma once
 
 #include "lspcg_internal.hpp"
@@ -86,6 +95,11 @@ constexpr int kSellXBlk = 16;   // vector entries per staged block
 // gathers they replace (us per iteration, SELL-64X vs SELL-64J: delaunay1m 127.0 vs 134.9, delaunay64k
 // 31.5 vs 28.6, bunny 18.8 vs 16.9; profiles/r6_sellx_probe.jsonl)
 constexpr int64_t kSellXMinN = 262144;
+// col_bits of the other layouts (with kSellJag / kSellJagX the `kind` numbers the C ABI reports)
+constexpr int kSellDia = 1;     // SELL-DIA, BSELL-DIA
+constexpr int kSellCoded = 8;   // SELL-64C
+constexpr int kSellOff16 = 16;  // SELL-64 / BSELL-64, 16-bit offsets
+constexpr int kSellInt32 = 32;  // SELL-64 / BSELL-64, int32 columns
 
 // Pattern shared by every matrix with the same CSR (rowptr, colind).
 //
@@ -109,7 +123,7 @@ struct SellPattern {
   int32_t* gp = nullptr;           // [ns+1] exclusive prefix of per-slice groups (slots) per row
   void* col = nullptr;             // [256*groups] (bs 1) / [64*groups] (bs 3) int32 columns or int16 offsets;
                                    // SELL-DIA (col_bits 1): [64*ns] uint16 row masks
-  int col_bits = 32;
+  int col_bits = kSellInt32;
   int32_t* dict = nullptr;         // SELL-DIA: [16*ns] ascending row-relative offsets per slice;
                                    // SELL-64C (col_bits 8): [64*ns], col = [256*groups] uint8 codes
   int32_t* rgp = nullptr;          // SELL-64C: [ns] group start in col2 of a slice kept uncoded, or -1
@@ -134,7 +148,7 @@ struct SellPattern {
   // entries of a value array of this pattern (sell_fill_values allocates this many)
   int64_t slots() const {
     if (bs == 3) return int64_t(576) * groups;  // BSELL-64 / BSELL-DIA: 9 values per block slot
-    return jagged() ? elems : (col_bits == 1 ? int64_t(64) : int64_t(256)) * groups;
+    return jagged() ? elems : (col_bits == kSellDia ? int64_t(64) : int64_t(256)) * groups;
   }
   void release() {  // the owned arrays (not rowptr)
     auto drop = [](auto*& p) {
@@ -151,7 +165,6 @@ struct SellArgs {
   int64_t ns;
   const int32_t* gp;
   const CT* col;
-  const int32_t* rowptr;
   const VT* vals;
   const int32_t* dict = nullptr;  // SELL-64C (CT = uint8_t): see kSellCodeMax
   const int32_t* rgp = nullptr;
@@ -172,6 +185,17 @@ struct SdiaArgs {
   const int32_t* dict;
   const VT* vals;
 };
+
+// the kernel arguments of a pattern and one of its value arrays (a layout's kernel reads its own fields)
+template <typename VT, typename CT>
+inline SellArgs<VT, CT> sell_args(const SellPattern& P, const void* vals) {
+  return {P.n,  P.ns,   P.gp, static_cast<const CT*>(P.col), static_cast<const VT*>(vals), P.dict, P.rgp, P.col2,
+          P.lmap, P.jc, P.xlp, P.xl, P.xn};
+}
+template <typename VT>
+inline SdiaArgs<VT> sdia_args(const SellPattern& P, const void* vals) {
+  return {P.n, P.ns, P.gp, static_cast<const uint16_t*>(P.col), P.dict, static_cast<const VT*>(vals)};
+}
 
 // ---- the SpMV ----------------------------------------------------------------
 template <typename VT>
@@ -203,6 +227,94 @@ struct epi_prefetch : std::false_type {};
 template <class E>
 struct epi_prefetch<E, std::void_t<decltype(E::PREFETCH)>> : std::bool_constant<E::PREFETCH> {};
 
+// K right-hand sides at once (k_spmm_sdia, k_spmv_sell with K > 1; launched by lspcg_multi.hip;
+// DESIGN.md §6 "Several right-hand sides").  The vectors are interleaved [n][K]: entry (row, column k)
+// at row * K + k, so the K entries one slot gathers are contiguous -- one load of K * sizeof(T) bytes
+// in 16-B parts (8 B for two floats).  A slot's value, column and live flag are loaded once and
+// applied to the K entries; per column the slots are added in the K = 1 order, so every column's row
+// sums are the single-vector kernel's bit for bit.  The epilogue's row() takes the K row sums; NDOT
+// counts all of its dots (K per reduced quantity).
+template <typename T, int K>
+struct RowK {
+  static constexpr int W = K * sizeof(T) >= 16 ? 16 / int(sizeof(T)) : K;  // entries per load
+  using V = T __attribute__((ext_vector_type(W)));
+  __device__ static __forceinline__ void load(const T* p, T (&v)[K]) {
+#pragma unroll
+    for (int c = 0; c < K / W; ++c) {
+      const V a = *(const __attribute__((address_space(1))) V*)(p + c * W);
+#pragma unroll
+      for (int w = 0; w < W; ++w) v[c * W + w] = a[w];
+    }
+  }
+  __device__ static __forceinline__ void store(T* p, const T (&v)[K]) {
+#pragma unroll
+    for (int c = 0; c < K / W; ++c) {
+      V a;
+#pragma unroll
+      for (int w = 0; w < W; ++w) a[w] = v[c * W + w];
+      *(__attribute__((address_space(1))) V*)(p + c * W) = a;
+    }
+  }
+};
+
+// the vector at column c: the gather functor's entry (K = 1) or the K entries of row c of its vector
+template <int K, typename T, class Gx>
+__device__ __forceinline__ void gather_k(const Gx& gx, int64_t c, T (&xv)[K]) {
+  if constexpr (K == 1) xv[0] = gx(c);
+  else RowK<T, K>::load(gx.x + c * K, xv);
+}
+
+// a stored column word that is an entry, not padding (kSellPad16 in 16-bit words, -1 in int32 columns)
+template <typename CT>
+__device__ __forceinline__ bool sell_real(int o) {
+  return sizeof(CT) == 2 ? o != kSellPad16 : o >= 0;
+}
+
+// A column word (a 16-bit offset from the slice's first row `base`, or an int32 column) -> the
+// column to gather and the live flag.  Padding and the words of a clamped surplus group (!in) gather
+// the slice's first row and are never added.
+template <typename CT>
+__device__ __forceinline__ void sell_word(int o, int32_t base, bool in, bool& m, int& c) {
+  static_assert(std::is_same<CT, int16_t>::value || std::is_same<CT, int32_t>::value, "16-bit offsets or int32 columns");
+  const bool real = sell_real<CT>(o);
+  m = real && in;
+  c = sizeof(CT) == 2 ? base + (real ? o : 0) : (real ? o : base);
+}
+// one 4-entry group's words, one 8- or 16-byte load
+template <typename CT>
+__device__ __forceinline__ void sell_decode(const CT* p, int32_t base, bool in, bool (&m)[4], int (&c)[4]) {
+  using V = CT __attribute__((ext_vector_type(4)));
+  const V cc = *(const __attribute__((address_space(1))) V*)(p);
+  const int o[4] = {cc.x, cc.y, cc.z, cc.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sell_word<CT>(o[j], base, in, m[j], c[j]);
+}
+
+// The hand-off of a lane's row sum (K = 1) or its K row sums to the epilogue.  prefetch() goes
+// before the slot loop: a PREFETCH epilogue's own-row value is loaded there and handed to row_pf().
+template <typename T, int K, class Epi>
+struct RowOut {
+  static constexpr bool PF = epi_prefetch<Epi>::value && K == 1;
+  T pf = T(0);
+  __device__ __forceinline__ void prefetch(Epi& epi, int64_t i, bool live) {
+    if constexpr (PF) {
+      if (live) pf = epi.prefetch(i);
+    }
+  }
+  __device__ __forceinline__ void emit(Epi& epi, int64_t i, bool live, T acc, DD* d) const {
+    if (!live) return;
+    if constexpr (PF) epi.row_pf(i, acc, d, pf);
+    else epi.row(i, acc, d);
+  }
+  __device__ __forceinline__ void emit(Epi& epi, int64_t i, bool live, const T (&acc)[K], DD* d) const {
+    if constexpr (K == 1) {
+      emit(epi, i, live, acc[0], d);
+    } else {
+      if (live) epi.row(i, acc, d);
+    }
+  }
+};
+
 // 256-thread workgroups = 4 slices = one 256-row tile (the same row tiles as k_spmv, so the
 // prologue / epilogue functors and the dot-product reduction are shared).  QB groups of 4
 // entries are loaded per lane before the first gather (branch-free: the group index is
@@ -210,11 +322,12 @@ struct epi_prefetch<E, std::void_t<decltype(E::PREFETCH)>> : std::bool_constant<
 // MINW: minimum workgroups per CU the register allocation must allow (6 x 256 threads for the
 // compact-value PCG kernels, whose reducing launches use a resident 6-per-CU grid; 1 for fp64
 // values and the double-gather fused epilogues, which need more registers than 6/CU leaves).
-template <typename T, typename VT, typename CT, int QB, int TH, int MINW, class Pro, class Gx, class Epi>
+// K > 1: K interleaved vectors (see RowK), K accumulators per lane; 16-bit offsets or int32 columns.
+template <typename T, typename VT, typename CT, int QB, int TH, int MINW, class Pro, class Gx, class Epi, int K = 1>
 __global__ void __launch_bounds__(TH, MINW) k_spmv_sell(SellArgs<VT, CT> a, Pro pro, Gx gx, Epi epi) {
   constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
-  constexpr bool C16 = std::is_same<CT, int16_t>::value;
   constexpr bool C8 = std::is_same<CT, uint8_t>::value;  // SELL-64C
+  static_assert(K == 1 || !C8, "SELL-64C has no K-vector kernel");
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
   const int64_t ntiles = (a.n + TH - 1) / TH;
@@ -254,11 +367,11 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sell(SellArgs<VT, CT> a, Pro 
       const VT* vp = a.vals + 256 * int64_t(g0) + 4 * lane;
       const CT* cp = a.col + 256 * int64_t(g0) + 4 * lane;
       [[maybe_unused]] const int16_t* cp2 = C8 ? a.col2 + 256 * int64_t(rg) + 4 * lane : nullptr;
-      T acc = T(0);
-      T pf = T(0);
-      if constexpr (epi_prefetch<Epi>::value) {
-        if (i < a.n) pf = epi.prefetch(i);
-      }
+      T acc[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = T(0);
+      RowOut<T, K, Epi> out;
+      out.prefetch(epi, i, i < a.n);
       for (int q0 = 0; q0 < nq; q0 += QB) {
         VT v[QB][4];
         int c[QB][4];
@@ -278,48 +391,27 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sell(SellArgs<VT, CT> a, Pro 
                 c[u][j] = b != kSellCodePad ? base + lane + off : base;  // padding gathers row base
               }
             } else {
-              const i16x4 cc = *(const __attribute__((address_space(1))) i16x4*)(cp2 + 256 * q);
-              const int o[4] = {cc.x, cc.y, cc.z, cc.w};
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                m[u][j] = (o[j] != kSellPad16) && (q0 + u < nq);
-                c[u][j] = base + (o[j] != kSellPad16 ? o[j] : 0);
-              }
-            }
-          } else if constexpr (C16) {
-            const i16x4 cc = *(const __attribute__((address_space(1))) i16x4*)(cp + 256 * q);
-            const int o[4] = {cc.x, cc.y, cc.z, cc.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              m[u][j] = (o[j] != kSellPad16) && (q0 + u < nq);
-              c[u][j] = base + (o[j] != kSellPad16 ? o[j] : 0);
+              sell_decode(cp2 + 256 * q, base, q0 + u < nq, m[u], c[u]);
             }
           } else {
-            const i32x4 cc = *(const __attribute__((address_space(1))) i32x4*)(cp + 256 * q);
-            const int o[4] = {cc.x, cc.y, cc.z, cc.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              m[u][j] = (o[j] >= 0) && (q0 + u < nq);
-              c[u][j] = o[j] >= 0 ? o[j] : base;
-            }
+            sell_decode(cp + 256 * q, base, q0 + u < nq, m[u], c[u]);
           }
         }
-        T xv[QB][4];
+        T xv[QB][4][K];
 #pragma unroll
         for (int u = 0; u < QB; ++u)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) xv[u][j] = gx(c[u][j]);
+          for (int j = 0; j < 4; ++j) gather_k<K>(gx, c[u][j], xv[u][j]);
 #pragma unroll
         for (int u = 0; u < QB; ++u)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            if (m[u][j]) acc = acc + T(v[u][j]) * xv[u][j];
+            if (m[u][j]) {
+#pragma unroll
+              for (int k = 0; k < K; ++k) acc[k] = acc[k] + T(v[u][j]) * xv[u][j][k];
+            }
       }
-      if constexpr (epi_prefetch<Epi>::value) {
-        if (i < a.n) epi.row_pf(i, acc, d, pf);
-      } else {
-        if (i < a.n) epi.row(i, acc, d);
-      }
+      out.emit(epi, i, i < a.n, acc, d);
     }
   }
   finish_epi_dots<Epi>(d, epi);
@@ -425,10 +517,8 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sellj(SellArgs<VT, int16_t> a
       const int32_t base = int32_t(s * kSellC);
       const int64_t i = int64_t(base) + rl;
       T acc = T(0);
-      T pf = T(0);
-      if constexpr (epi_prefetch<Epi>::value) {
-        if (i < a.n) pf = epi.prefetch(i);
-      }
+      RowOut<T, 1, Epi> out;
+      out.prefetch(epi, i, i < a.n);
       bool have = (c0 & 0xffu) != 0;
       while (have) {  // wave-uniform: software-pipelined, the next batch's loads beside this one's gathers
         const bool more = (lo & 0xffu) != 0;
@@ -441,7 +531,7 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sellj(SellArgs<VT, int16_t> a
           const int o[4] = {cur.cc[u].x, cur.cc[u].y, cur.cc[u].z, cur.cc[u].w};
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            m[u][j] = o[j] != kSellPad16;
+            m[u][j] = sell_real<int16_t>(o[j]);
             if constexpr (XS) xv[u][j] = sx[m[u][j] ? o[j] : 0];
             else xv[u][j] = gx(base + (m[u][j] ? o[j] : 0));
           }
@@ -454,258 +544,7 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sellj(SellArgs<VT, int16_t> a
         if (more) cur = nxt;
         have = more;
       }
-      if constexpr (epi_prefetch<Epi>::value) {
-        if (i < a.n) epi.row_pf(i, acc, d, pf);
-      } else {
-        if (i < a.n) epi.row(i, acc, d);
-      }
-    }
-  }
-  finish_epi_dots<Epi>(d, epi);
-}
-
-// SELL-DIA SpMV (layout: see kSdiaMax): one wave = one 64-row slice of a 256-row tile, SB slots
-// per batch, every load of a batch issued before the first add (value loads and vector loads are
-// independent: the slot's offset is a scalar).  A slice's metadata -- its slot range (gp), its
-// whole 16-entry offset dictionary (one scalar block load: entries past the slice's count are
-// never used, masked lanes read x[base]) and its row masks -- is loaded in one batch, and the
-// first tile's batch before the prologue's state read: one memory latency before the value /
-// vector loads instead of three in a row (state, gp, dictionary).
-template <typename T, typename VT, int SB, int TH, int MINW, class Pro, class Gx, class Epi>
-__global__ void __launch_bounds__(TH, MINW) k_spmv_sdia(SdiaArgs<VT> a, Pro pro, Gx gx, Epi epi) {
-  constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
-  const int64_t ntiles = (a.n + TH - 1) / TH;
-  int32_t g0 = 0, g1 = 0;
-  unsigned msk = 0;
-  int32_t dct[kSdiaMax];
-  auto meta = [&](int64_t sl) {
-    g0 = a.gp[sl];
-    g1 = a.gp[sl + 1];
-    msk = gld(a.mask + kSellC * sl + lane);
-    const int32_t* dp = a.dict + kSdiaMax * sl;
-#pragma unroll
-    for (int j = 0; j < kSdiaMax; ++j) dct[j] = dp[j];
-  };
-  {
-    const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
-    if (int64_t(blockIdx.x) < ntiles && s < a.ns) meta(s);
-  }
-  if (pro.exit()) return;
-  gx.prepare();
-  epi.prepare();
-  DD d[ND];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) d[j] = dd_zero();
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t s = tile * (TH / 64) + w;
-    const int64_t i = tile * TH + threadIdx.x;
-    if (s < a.ns) {  // wave-uniform
-      if (tile != int64_t(blockIdx.x)) meta(s);
-      const int nd = g1 - g0;
-      const int32_t base = int32_t(s * kSellC);
-      const int32_t row = base + lane;
-      T acc = T(0);
-      T pf = T(0);
-      if constexpr (epi_prefetch<Epi>::value) {
-        if (i < a.n) pf = epi.prefetch(i);
-      }
-#pragma unroll
-      for (int j0 = 0; j0 < kSdiaMax; j0 += SB) {
-        if (j0 >= nd) break;  // wave-uniform
-        VT v[SB];
-        T xv[SB];
-        bool m[SB];
-#pragma unroll
-        for (int u = 0; u < SB; ++u) {
-          const int j = j0 + u;
-          m[u] = (j < nd) && ((msk >> j) & 1u);
-          const int32_t c = m[u] ? row + dct[j] : base;
-          v[u] = gld(a.vals + kSellC * int64_t(g0 + min(j, nd - 1)) + lane);
-          xv[u] = gx(c);
-        }
-#pragma unroll
-        for (int u = 0; u < SB; ++u)
-          if (m[u]) acc = acc + T(v[u]) * xv[u];
-      }
-      if constexpr (epi_prefetch<Epi>::value) {
-        if (i < a.n) epi.row_pf(i, acc, d, pf);
-      } else {
-        if (i < a.n) epi.row(i, acc, d);
-      }
-    }
-  }
-  finish_epi_dots<Epi>(d, epi);
-}
-
-// ---- K right-hand sides at once (lspcg_multi.hip; DESIGN.md §6 "Several right-hand sides") ----
-// The vectors are interleaved [n][K]: entry (row, column k) at row * K + k, so the K entries one
-// slot gathers are contiguous -- one load of K * sizeof(T) bytes in 16-B parts (8 B for two floats).
-template <typename T, int K>
-struct RowK {
-  static constexpr int W = K * sizeof(T) >= 16 ? 16 / int(sizeof(T)) : K;  // entries per load
-  using V = T __attribute__((ext_vector_type(W)));
-  __device__ static __forceinline__ void load(const T* p, T (&v)[K]) {
-#pragma unroll
-    for (int c = 0; c < K / W; ++c) {
-      const V a = *(const __attribute__((address_space(1))) V*)(p + c * W);
-#pragma unroll
-      for (int w = 0; w < W; ++w) v[c * W + w] = a[w];
-    }
-  }
-  __device__ static __forceinline__ void store(T* p, const T (&v)[K]) {
-#pragma unroll
-    for (int c = 0; c < K / W; ++c) {
-      V a;
-#pragma unroll
-      for (int w = 0; w < W; ++w) a[w] = v[c * W + w];
-      *(__attribute__((address_space(1))) V*)(p + c * W) = a;
-    }
-  }
-};
-
-// SELL-DIA SpMV of K interleaved vectors: k_spmv_sdia with K accumulators per lane.  A slot's
-// value, offset and mask bit are loaded once and applied to the K entries of the gathered row;
-// per column the slots are added in k_spmv_sdia's order, so every column's row sums are the
-// single-vector kernel's bit for bit.  The epilogue's row() takes the K row sums; NDOT counts
-// all of its dots (K per reduced quantity).
-template <typename T, typename VT, int K, int SB, int TH, class Pro, class Epi>
-__global__ void __launch_bounds__(TH) k_spmm_sdia(SdiaArgs<VT> a, const T* __restrict__ x, Pro pro, Epi epi) {
-  constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
-  const int64_t ntiles = (a.n + TH - 1) / TH;
-  int32_t g0 = 0, g1 = 0;
-  unsigned msk = 0;
-  int32_t dct[kSdiaMax];
-  auto meta = [&](int64_t sl) {
-    g0 = a.gp[sl];
-    g1 = a.gp[sl + 1];
-    msk = gld(a.mask + kSellC * sl + lane);
-    const int32_t* dp = a.dict + kSdiaMax * sl;
-#pragma unroll
-    for (int j = 0; j < kSdiaMax; ++j) dct[j] = dp[j];
-  };
-  {
-    const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
-    if (int64_t(blockIdx.x) < ntiles && s < a.ns) meta(s);
-  }
-  if (pro.exit()) return;
-  DD d[ND];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) d[j] = dd_zero();
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t s = tile * (TH / 64) + w;
-    const int64_t i = tile * TH + threadIdx.x;
-    if (s < a.ns) {  // wave-uniform
-      if (tile != int64_t(blockIdx.x)) meta(s);
-      const int nd = g1 - g0;
-      const int32_t base = int32_t(s * kSellC);
-      const int32_t row = base + lane;
-      T acc[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) acc[k] = T(0);
-#pragma unroll
-      for (int j0 = 0; j0 < kSdiaMax; j0 += SB) {
-        if (j0 >= nd) break;  // wave-uniform
-        VT v[SB];
-        T xv[SB][K];
-        bool m[SB];
-#pragma unroll
-        for (int u = 0; u < SB; ++u) {
-          const int j = j0 + u;
-          m[u] = (j < nd) && ((msk >> j) & 1u);
-          const int32_t c = m[u] ? row + dct[j] : base;
-          v[u] = gld(a.vals + kSellC * int64_t(g0 + min(j, nd - 1)) + lane);
-          RowK<T, K>::load(x + int64_t(c) * K, xv[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < SB; ++u)
-          if (m[u]) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) acc[k] = acc[k] + T(v[u]) * xv[u][k];
-          }
-      }
-      if (i < a.n) epi.row(i, acc, d);
-    }
-  }
-  finish_epi_dots<Epi>(d, epi);
-}
-
-// SELL-64 SpMV (16-bit offsets or int32 columns) of K interleaved vectors: k_spmv_sell with K
-// accumulators per lane, QB groups of 4 entries per batch, the same slot order per column.
-template <typename T, typename VT, typename CT, int K, int QB, int TH, class Pro, class Epi>
-__global__ void __launch_bounds__(TH) k_spmm_sell(SellArgs<VT, CT> a, const T* __restrict__ x, Pro pro, Epi epi) {
-  static_assert(std::is_same<CT, int16_t>::value || std::is_same<CT, int32_t>::value, "16-bit offsets or int32 columns");
-  constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
-  constexpr bool C16 = std::is_same<CT, int16_t>::value;
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int64_t ntiles = (a.n + TH - 1) / TH;
-  int32_t gb[2] = {0, 0};
-  if (int64_t(blockIdx.x) * (TH / 64) + w < a.ns) {
-    gb[0] = a.gp[int64_t(blockIdx.x) * (TH / 64) + w];
-    gb[1] = a.gp[int64_t(blockIdx.x) * (TH / 64) + w + 1];
-  }
-  if (pro.exit()) return;
-  DD d[ND];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) d[j] = dd_zero();
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t s = tile * (TH / 64) + w;
-    const int64_t i = tile * TH + threadIdx.x;
-    if (s < a.ns) {  // wave-uniform
-      if (tile != int64_t(blockIdx.x)) {
-        gb[0] = a.gp[s];
-        gb[1] = a.gp[s + 1];
-      }
-      const int32_t g0 = gb[0];
-      const int nq = gb[1] - g0;
-      const int32_t base = int32_t(s * kSellC);
-      const VT* vp = a.vals + 256 * int64_t(g0) + 4 * lane;
-      const CT* cp = a.col + 256 * int64_t(g0) + 4 * lane;
-      T acc[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) acc[k] = T(0);
-      for (int q0 = 0; q0 < nq; q0 += QB) {
-        VT v[QB][4];
-        int c[QB][4];
-        bool m[QB][4];
-#pragma unroll
-        for (int u = 0; u < QB; ++u) {
-          const int q = min(q0 + u, nq - 1);
-          Vec4Ld<VT>::load(vp + 256 * q, v[u]);
-          int o[4];
-          if constexpr (C16) {
-            const i16x4 cc = *(const __attribute__((address_space(1))) i16x4*)(cp + 256 * q);
-            o[0] = cc.x; o[1] = cc.y; o[2] = cc.z; o[3] = cc.w;
-          } else {
-            const i32x4 cc = *(const __attribute__((address_space(1))) i32x4*)(cp + 256 * q);
-            o[0] = cc.x; o[1] = cc.y; o[2] = cc.z; o[3] = cc.w;
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const bool real = C16 ? o[j] != kSellPad16 : o[j] >= 0;
-            m[u][j] = real && (q0 + u < nq);
-            c[u][j] = real ? (C16 ? base + o[j] : o[j]) : base;  // padding gathers the slice's first row
-          }
-        }
-        T xv[QB][4][K];
-#pragma unroll
-        for (int u = 0; u < QB; ++u)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) RowK<T, K>::load(x + int64_t(c[u][j]) * K, xv[u][j]);
-#pragma unroll
-        for (int u = 0; u < QB; ++u)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (m[u][j]) {
-#pragma unroll
-              for (int k = 0; k < K; ++k) acc[k] = acc[k] + T(v[u][j]) * xv[u][j][k];
-            }
-      }
-      if (i < a.n) epi.row(i, acc, d);
+      out.emit(epi, i, i < a.n, acc, d);
     }
   }
   finish_epi_dots<Epi>(d, epi);
@@ -747,7 +586,6 @@ __device__ __forceinline__ void bsell_load_block(const float* slot, float (&v)[9
 template <typename T, typename VT, typename CT, int QB, int TH, int MINW, class Pro, class Gx, class Epi>
 __global__ void __launch_bounds__(TH, MINW) k_spmv_bsell3(SellArgs<VT, CT> a, Pro pro, Gx gx, Epi epi) {
   constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
-  constexpr bool C16 = sizeof(CT) == 2;
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
   const int64_t nb = a.n / 3;
@@ -786,13 +624,7 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_bsell3(SellArgs<VT, CT> a, Pr
           const int q = min(q0 + u, nq - 1);
           bsell_load_block(vp + 576 * q, v[u]);
           const int o = int(gld(cp + 64 * q));
-          if constexpr (C16) {
-            m[u] = (o != kSellPad16) && (q0 + u < nq);
-            c[u] = base + (o != kSellPad16 ? o : 0);
-          } else {
-            m[u] = (o >= 0) && (q0 + u < nq);
-            c[u] = o >= 0 ? o : base;
-          }
+          sell_word<CT>(o, base, q0 + u < nq, m[u], c[u]);
         }
         T xv[QB][3];
 #pragma unroll
@@ -817,12 +649,149 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_bsell3(SellArgs<VT, CT> a, Pr
   finish_epi_dots<Epi>(d, epi);
 }
 
+// A SELL-DIA / BSELL-DIA slice's metadata: its slot range (gp), its whole 16-entry offset dictionary
+// (one scalar block load: entries past the slice's count are never used, masked lanes read x[base])
+// and the lane's row mask, loaded in one batch.
+struct SdiaSlice {
+  int32_t g0 = 0, g1 = 0;
+  unsigned msk = 0;
+  int32_t dct[kSdiaMax];
+  template <typename VT>
+  __device__ __forceinline__ void load(const SdiaArgs<VT>& a, int64_t sl, int lane) {
+    g0 = a.gp[sl];
+    g1 = a.gp[sl + 1];
+    msk = gld(a.mask + kSellC * sl + lane);
+    const int32_t* dp = a.dict + kSdiaMax * sl;
+#pragma unroll
+    for (int j = 0; j < kSdiaMax; ++j) dct[j] = dp[j];
+  }
+  // slot j of a batch: whether this lane's row has it (nd = the slice's slot count), and where its
+  // values start (clamped: the surplus slots of the last batch load the last slot and are masked)
+  __device__ __forceinline__ bool has(int j, int nd) const { return (j < nd) && ((msk >> j) & 1u); }
+  __device__ __forceinline__ int64_t slot(int j, int nd) const { return int64_t(g0 + min(j, nd - 1)); }
+};
+
+// SELL-DIA SpMV (layout: see kSdiaMax): one wave = one 64-row slice of a 256-row tile, SB slots
+// per batch, every load of a batch issued before the first add (value loads and vector loads are
+// independent: the slot's offset is a scalar).  The first tile's metadata is loaded before the
+// prologue's state read: one memory latency before the value / vector loads instead of three in a
+// row (state, gp, dictionary).
+template <typename T, typename VT, int SB, int TH, int MINW, class Pro, class Gx, class Epi>
+__global__ void __launch_bounds__(TH, MINW) k_spmv_sdia(SdiaArgs<VT> a, Pro pro, Gx gx, Epi epi) {
+  constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t ntiles = (a.n + TH - 1) / TH;
+  SdiaSlice sl;
+  {
+    const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
+    if (int64_t(blockIdx.x) < ntiles && s < a.ns) sl.load(a, s, lane);
+  }
+  if (pro.exit()) return;
+  gx.prepare();
+  epi.prepare();
+  DD d[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) d[j] = dd_zero();
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t s = tile * (TH / 64) + w;
+    const int64_t i = tile * TH + threadIdx.x;
+    if (s < a.ns) {  // wave-uniform
+      if (tile != int64_t(blockIdx.x)) sl.load(a, s, lane);
+      const int nd = sl.g1 - sl.g0;
+      const int32_t base = int32_t(s * kSellC);
+      const int32_t row = base + lane;
+      T acc = T(0);
+      RowOut<T, 1, Epi> out;
+      out.prefetch(epi, i, i < a.n);
+#pragma unroll
+      for (int j0 = 0; j0 < kSdiaMax; j0 += SB) {
+        if (j0 >= nd) break;  // wave-uniform
+        VT v[SB];
+        T xv[SB];
+        bool m[SB];
+#pragma unroll
+        for (int u = 0; u < SB; ++u) {
+          const int j = j0 + u;
+          m[u] = sl.has(j, nd);
+          const int32_t c = m[u] ? row + sl.dct[j] : base;
+          v[u] = gld(a.vals + kSellC * sl.slot(j, nd) + lane);
+          xv[u] = gx(c);
+        }
+#pragma unroll
+        for (int u = 0; u < SB; ++u)
+          if (m[u]) acc = acc + T(v[u]) * xv[u];
+      }
+      out.emit(epi, i, i < a.n, acc, d);
+    }
+  }
+  finish_epi_dots<Epi>(d, epi);
+}
+
+// SELL-DIA SpMV of K interleaved vectors (see RowK): k_spmv_sdia's walk with K accumulators per
+// lane.  A kernel of its own, with the vector as a restrict pointer argument and no
+// minimum-workgroups bound: as a K parameter of k_spmv_sdia (the vector inside the gather functor,
+// after the prologue's argument) the same loop measured 0.6-2.4 % slower per solve on systems of
+// 65 k - 70 k rows (profiles/sell_kernels_refactor_ab.json, "k_merged_into_k_spmv_sdia").
+template <typename T, typename VT, int K, int SB, int TH, class Pro, class Epi>
+__global__ void __launch_bounds__(TH) k_spmm_sdia(SdiaArgs<VT> a, const T* __restrict__ x, Pro pro, Epi epi) {
+  constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t ntiles = (a.n + TH - 1) / TH;
+  SdiaSlice sl;
+  {
+    const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
+    if (int64_t(blockIdx.x) < ntiles && s < a.ns) sl.load(a, s, lane);
+  }
+  if (pro.exit()) return;
+  DD d[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) d[j] = dd_zero();
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t s = tile * (TH / 64) + w;
+    const int64_t i = tile * TH + threadIdx.x;
+    if (s < a.ns) {  // wave-uniform
+      if (tile != int64_t(blockIdx.x)) sl.load(a, s, lane);
+      const int nd = sl.g1 - sl.g0;
+      const int32_t base = int32_t(s * kSellC);
+      const int32_t row = base + lane;
+      T acc[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = T(0);
+#pragma unroll
+      for (int j0 = 0; j0 < kSdiaMax; j0 += SB) {
+        if (j0 >= nd) break;  // wave-uniform
+        VT v[SB];
+        T xv[SB][K];
+        bool m[SB];
+#pragma unroll
+        for (int u = 0; u < SB; ++u) {
+          const int j = j0 + u;
+          m[u] = sl.has(j, nd);
+          const int32_t c = m[u] ? row + sl.dct[j] : base;
+          v[u] = gld(a.vals + kSellC * sl.slot(j, nd) + lane);
+          RowK<T, K>::load(x + int64_t(c) * K, xv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < SB; ++u)
+          if (m[u]) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[k] = acc[k] + T(v[u]) * xv[u][k];
+          }
+      }
+      if (i < a.n) epi.row(i, acc, d);
+    }
+  }
+  finish_epi_dots<Epi>(d, epi);
+}
+
 // BSR 3x3 over the BSELL-DIA layout (SELL-DIA's slot dictionary on the block graph + BSELL-64's
-// 9-value lane chunks): one lane = one block row = 3 scalar rows; slot j of the slice holds the
-// block at block column I + dict[j] (mask bit j), so the x entries of a slot are three contiguous
-// 64-block loads at a wave-uniform offset and no column is loaded at all.  SB slots per batch, all
-// value and x loads of a batch issued before the first add; the slot order is the row's block
-// column order, c = 0, 1, 2 inside a block: the expanded scalar CSR's summation order.
+// 9-value lane chunks): k_spmv_sdia's walk with one lane = one block row = 3 scalar rows; slot j of
+// the slice holds the block at block column I + dict[j] (mask bit j), so the x entries of a slot
+// are three contiguous 64-block loads at a wave-uniform offset and no column is loaded at all.  The
+// slot order is the row's block column order, c = 0, 1, 2 inside a block: the expanded scalar CSR's
+// summation order.
 template <typename T, typename VT, int SB, int TH, int MINW, class Pro, class Gx, class Epi>
 __global__ void __launch_bounds__(TH, MINW) k_spmv_bsdia3(SdiaArgs<VT> a, Pro pro, Gx gx, Epi epi) {
   constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
@@ -830,20 +799,10 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_bsdia3(SdiaArgs<VT> a, Pro pr
   const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
   const int64_t nb = a.n / 3;
   const int64_t ntiles = (nb + TH - 1) / TH;
-  int32_t g0 = 0, g1 = 0;
-  unsigned msk = 0;
-  int32_t dct[kSdiaMax];
-  auto meta = [&](int64_t sl) {
-    g0 = a.gp[sl];
-    g1 = a.gp[sl + 1];
-    msk = gld(a.mask + kSellC * sl + lane);
-    const int32_t* dp = a.dict + kSdiaMax * sl;
-#pragma unroll
-    for (int j = 0; j < kSdiaMax; ++j) dct[j] = dp[j];
-  };
+  SdiaSlice sl;
   {
     const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
-    if (int64_t(blockIdx.x) < ntiles && s < a.ns) meta(s);
+    if (int64_t(blockIdx.x) < ntiles && s < a.ns) sl.load(a, s, lane);
   }
   if (pro.exit()) return;
   gx.prepare();
@@ -855,8 +814,8 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_bsdia3(SdiaArgs<VT> a, Pro pr
     const int64_t s = tile * (TH / 64) + w;
     const int64_t I = tile * TH + threadIdx.x;
     if (s < a.ns) {  // wave-uniform
-      if (tile != int64_t(blockIdx.x)) meta(s);
-      const int nd = g1 - g0;
+      if (tile != int64_t(blockIdx.x)) sl.load(a, s, lane);
+      const int nd = sl.g1 - sl.g0;
       const int32_t base = int32_t(s * kSellC);
       const int32_t brow = base + lane;
       T acc[3] = {T(0), T(0), T(0)};
@@ -869,9 +828,9 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_bsdia3(SdiaArgs<VT> a, Pro pr
 #pragma unroll
         for (int u = 0; u < SB; ++u) {
           const int j = j0 + u;
-          m[u] = (j < nd) && ((msk >> j) & 1u);
-          const int64_t c = 3 * int64_t(m[u] ? brow + dct[j] : base);
-          bsell_load_block(a.vals + 576 * int64_t(g0 + min(j, nd - 1)), v[u]);
+          m[u] = sl.has(j, nd);
+          const int64_t c = 3 * int64_t(m[u] ? brow + sl.dct[j] : base);
+          bsell_load_block(a.vals + 576 * sl.slot(j, nd), v[u]);
 #pragma unroll
           for (int cc = 0; cc < 3; ++cc) xv[u][cc] = gx(c + cc);
         }
@@ -918,147 +877,119 @@ inline double sell_max_pad() {
   return v;
 }
 
-// grid of a SELL launch (the solver sizes the split-reduction groups from it)
+// ---- the launch ----------------------------------------------------------------
 constexpr int kSellWG = 256;  // 4 slices per workgroup (512 / 1024 measured slower: DESIGN.md §5)
-constexpr int kSdiaSB = 8;    // SELL-DIA slots per batch
 
-inline int64_t sell_grid(const SellPattern& P, bool reducing) {
-  return std::min<int64_t>((P.nb + kSellWG - 1) / kSellWG, sell_cap(reducing));
+// Grid of a SELL launch: one workgroup per row tile of 256 scalar (bs 1) or block (bs 3) rows, capped
+// by sell_cap (the solver sizes the split-reduction groups from it).  one_tile_per_wg (batched
+// solves): never capped -- workgroup b owns exactly row tile b, so its dot partial is that tile's
+// and its prologue may test the tile's own system.
+inline int64_t sell_grid(const SellPattern& P, bool reducing, bool one_tile_per_wg = false) {
+  const int64_t tiles = (P.nb + kSellWG - 1) / kSellWG;
+  return one_tile_per_wg ? tiles : std::min<int64_t>(tiles, sell_cap(reducing));
 }
 
-template <typename T, typename VT, typename CT, int TH, class Pro, class Gx, class Epi>
-inline void launch_spmv_sell_th(const SellPattern& P, const void* vals, Gx gx, Pro pro, Epi epi, hipStream_t st,
-                                bool one_tile_per_wg = false) {
-  int64_t grid = (P.nb + TH - 1) / TH;  // row tiles: TH scalar rows (bs 1) or TH block rows (bs 3)
-  // one_tile_per_wg (batched solves): workgroup b owns exactly row tile b, so its dot partial is
-  // that tile's and its prologue may test the tile's own system
-  if (!one_tile_per_wg) grid = std::min<int64_t>(grid, sell_cap(Epi::NDOT > 0));
-  if (grid <= 0) return;
-  SellArgs<VT, CT> a{P.n,      P.ns,  P.gp,  static_cast<const CT*>(P.col), P.rowptr, static_cast<const VT*>(vals),
-                     P.dict, P.rgp, P.col2};
-  // compact-value kernels: registers for 6 workgroups per CU (the resident reducing grid)
-  constexpr int MINW = (sizeof(VT) == 4 && std::is_same<Gx, GatherVec<T>>::value) ? (TH <= 1536 ? 1536 / TH : 1) : 1;
-  if constexpr (!std::is_same<CT, uint16_t>::value && !std::is_same<CT, uint8_t>::value) {  // BSELL-64: int16 / int32 columns
-    if (P.bs == 3) {
-      // 2 block slots (18 values, 6 gathers) per batch
-      LSPCG_LAUNCH_SPMV((k_spmv_bsell3<T, VT, CT, 2, TH, MINW, Pro, Gx, Epi>), dim3(unsigned(grid)), dim3(TH), 0, st,
-                         a, pro, gx, epi);
-      return;
-    }
-  }
-  // 2 groups of 4 entries per batch (tools/sell_sweep.py on kuhn101, dictionary columns, cold:
-  // fp64 values 32.2 us vs 33.8 with 4 groups and 46.0 with 8; fp32 values 22.7 vs 24.1 / 37.0)
-  constexpr int QB = 2;
-  LSPCG_LAUNCH_SPMV((k_spmv_sell<T, VT, CT, QB, TH, MINW, Pro, Gx, Epi>), dim3(unsigned(grid)), dim3(TH), 0, st, a,
-                     pro, gx, epi);
-}
-
-// SELL-DIA launch
-template <typename T, typename VT, class Pro, class Gx, class Epi>
-inline void launch_spmv_sdia(const SellPattern& P, const void* vals, Gx gx, Pro pro, Epi epi, hipStream_t st,
-                             bool one_tile_per_wg = false) {
-  int64_t grid = (P.nb + kSellWG - 1) / kSellWG;
-  if (!one_tile_per_wg) grid = std::min<int64_t>(grid, sell_cap(Epi::NDOT > 0));
-  if (grid <= 0) return;
-  SdiaArgs<VT> a{P.n, P.ns, P.gp, static_cast<const uint16_t*>(P.col), P.dict, static_cast<const VT*>(vals)};
-  constexpr int MINW = (sizeof(VT) <= 4 && std::is_same<Gx, GatherVec<T>>::value) ? 1536 / kSellWG : 1;
-  LSPCG_LAUNCH_SPMV((k_spmv_sdia<T, VT, kSdiaSB, kSellWG, MINW, Pro, Gx, Epi>), dim3(unsigned(grid)), dim3(kSellWG),
-                     0, st, a, pro, gx, epi);
-}
-
-// BSELL-DIA launch: 256 block rows (4 slices) per row tile, as BSELL-64
+// Entries in flight per lane and batch.
+constexpr int kSdiaSB = 8;   // SELL-DIA slots
+// SELL-64 / SELL-64C: 2 groups of 4 entries (tools/sell_sweep.py on kuhn101, dictionary columns, cold:
+// fp64 values 32.2 us vs 33.8 with 4 groups and 46.0 with 8; fp32 values 22.7 vs 24.1 / 37.0)
+constexpr int kSellQB = 2;
+constexpr int kBsellQB = 2;  // BSELL-64 block slots (18 values, 6 gathers)
 #ifndef LSPCG_BSDIA_SB64
 #define LSPCG_BSDIA_SB64 2
 #endif
 #ifndef LSPCG_BSDIA_SB32
 #define LSPCG_BSDIA_SB32 2
 #endif
-// block slots per batch (2: 18 values, 6 x loads) by value size
+// BSELL-DIA block slots (2: 18 values, 6 x loads) by value size
 template <typename VT>
 constexpr int bsdia_sb() { return sizeof(VT) == 8 ? LSPCG_BSDIA_SB64 : LSPCG_BSDIA_SB32; }
-template <typename T, typename VT, class Pro, class Gx, class Epi>
-inline void launch_spmv_bsdia3(const SellPattern& P, const void* vals, Gx gx, Pro pro, Epi epi, hipStream_t st,
-                               bool one_tile_per_wg = false) {
-  int64_t grid = (P.nb + kSellWG - 1) / kSellWG;
-  if (!one_tile_per_wg) grid = std::min<int64_t>(grid, sell_cap(Epi::NDOT > 0));
-  if (grid <= 0) return;
-  SdiaArgs<VT> a{P.n, P.ns, P.gp, static_cast<const uint16_t*>(P.col), P.dict, static_cast<const VT*>(vals)};
-  constexpr int MINW = (sizeof(VT) == 4 && std::is_same<Gx, GatherVec<T>>::value) ? 1536 / kSellWG : 1;
-  LSPCG_LAUNCH_SPMV((k_spmv_bsdia3<T, VT, bsdia_sb<VT>(), kSellWG, MINW, Pro, Gx, Epi>), dim3(unsigned(grid)),
-                     dim3(kSellWG), 0, st, a, pro, gx, epi);
-}
-
-// SELL-64J / SELL-64X launch: 256-row tiles (4 slices), the SELL-64 grid rules
 #ifndef LSPCG_JAG_QB
-#define LSPCG_JAG_QB 2  // groups of 4 entries per batch
+#define LSPCG_JAG_QB 2  // SELL-64J / SELL-64X groups of 4 entries
 #endif
-template <typename T, typename VT, class Pro, class Gx, class Epi>
-inline void launch_spmv_sellj(const SellPattern& P, const void* vals, Gx gx, Pro pro, Epi epi, hipStream_t st,
-                              bool one_tile_per_wg = false) {
-  int64_t grid = (P.nb + kSellWG - 1) / kSellWG;
-  if (!one_tile_per_wg) grid = std::min<int64_t>(grid, sell_cap(Epi::NDOT > 0));
-  if (grid <= 0) return;
-  SellArgs<VT, int16_t> a{P.n, P.ns, P.gp, static_cast<const int16_t*>(P.col), P.rowptr, static_cast<const VT*>(vals)};
-  a.lmap = P.lmap;
-  a.jc = P.jc;
-  a.xlp = P.xlp;
-  a.xl = P.xl;
-  a.xn = P.xn;
-  constexpr int MINW = (sizeof(VT) == 4 && std::is_same<Gx, GatherVec<T>>::value) ? 1536 / kSellWG : 1;
-  if constexpr (std::is_same<Gx, GatherVec<T>>::value) {
-    if (P.col_bits == kSellJagX) {
-      const size_t lds = size_t(P.kx) * kSellXBlk * sizeof(T);
-      LSPCG_LAUNCH_SPMV((k_spmv_sellj<T, VT, LSPCG_JAG_QB, kSellWG, MINW, true, Pro, Gx, Epi>), dim3(unsigned(grid)), dim3(kSellWG),
-                         lds, st, a, pro, gx, epi);
-      return;
-    }
-  }
-  if (P.col_bits != kSellJag) return;  // (SELL-64X needs a plain vector gather: sell_build_pattern's callers)
-  LSPCG_LAUNCH_SPMV((k_spmv_sellj<T, VT, LSPCG_JAG_QB, kSellWG, MINW, false, Pro, Gx, Epi>), dim3(unsigned(grid)), dim3(kSellWG),
-                     0, st, a, pro, gx, epi);
-}
-
-template <typename T, typename VT, class Pro, class Gx, class Epi>
-inline void launch_spmv_sell_cfg(const SellPattern& P, const void* vals, Gx gx, Pro pro, Epi epi, hipStream_t st,
-                                 bool one_tile_per_wg = false) {
-  if (P.jagged()) launch_spmv_sellj<T, VT>(P, vals, gx, pro, epi, st, one_tile_per_wg);
-  else if (P.col_bits == 1 && P.bs == 3) launch_spmv_bsdia3<T, VT>(P, vals, gx, pro, epi, st, one_tile_per_wg);
-  else if (P.col_bits == 1) launch_spmv_sdia<T, VT>(P, vals, gx, pro, epi, st, one_tile_per_wg);
-  else if (P.col_bits == 16) launch_spmv_sell_th<T, VT, int16_t, kSellWG>(P, vals, gx, pro, epi, st, one_tile_per_wg);
-  else if (P.col_bits == 8) launch_spmv_sell_th<T, VT, uint8_t, kSellWG>(P, vals, gx, pro, epi, st, one_tile_per_wg);
-  else launch_spmv_sell_th<T, VT, int32_t, kSellWG>(P, vals, gx, pro, epi, st, one_tile_per_wg);
-}
-
-// K-vector launches.  SELL-DIA batches 8 / 8 / 4 slots for K = 2 / 4 / 8 (<= 32 vector entries of
+// K vectors: SELL-DIA batches 8 / 8 / 4 slots for K = 2 / 4 / 8 (<= 32 vector entries of
 // K * sizeof(T) bytes in flight per lane: mid-size systems run one wave per SIMD, so a lane's own
 // loads in flight, not occupancy, hide the latency there; half as many slots measured a few per
 // cent slower on Poisson 256^2); SELL-64 batches two 4-entry groups for K = 2 and one for K = 4, 8.
-// Register counts and occupancy: DESIGN.md §6.  Scalar patterns of kind SELL-DIA, 16-bit offsets
-// or int32 columns only; false for any other kind (nothing is launched).
+// Register counts and occupancy: DESIGN.md §6.
 template <int K>
 constexpr int spmm_sb() { return K == 8 ? 4 : 8; }
 template <int K>
 constexpr int spmm_qb() { return K == 2 ? 2 : 1; }
+// the layouts with a K-vector kernel: scalar SELL-DIA, 16-bit offsets, int32 columns
 inline bool spmm_supported(const SellPattern& P) {
-  return P.bs == 1 && (P.col_bits == 1 || P.col_bits == 16 || P.col_bits == 32);
+  return P.bs == 1 && (P.col_bits == kSellDia || P.col_bits == kSellOff16 || P.col_bits == kSellInt32);
 }
-template <typename T, typename VT, int K, class Pro, class Epi>
-inline bool launch_spmm_cfg(const SellPattern& P, const void* vals, const T* x, Pro pro, Epi epi, hipStream_t st) {
-  if (!spmm_supported(P)) return false;
-  const int64_t grid = std::min<int64_t>((P.nb + kSellWG - 1) / kSellWG, sell_cap(Epi::NDOT > 0));
-  if (grid <= 0) return true;
+
+// The one launch of every SELL kernel: y = epi(A gx) over pattern P with the value array `vals`
+// (VT: its type), K = 1 vector or K interleaved ones (gx.x is then [n][K]).  Dispatches over the
+// layout (col_bits, bs); a layout / gather / K combination without a kernel is an error
+// (LSPCG_ERR_UNSUPPORTED), never a silent return.
+// MINW, the workgroups per CU the registers must allow: 6 x 256 threads for the compact-value
+// kernels over a plain vector (the resident reducing grid); 1 for fp64 values, the double-gather
+// fused epilogues and the K-vector kernels, which need more registers than 6 per CU leaves.
+template <typename T, typename VT, int K = 1, class Pro, class Gx, class Epi>
+inline int launch_sell(const SellPattern& P, const void* vals, Gx gx, Pro pro, Epi epi, hipStream_t st,
+                       bool one_tile_per_wg = false) {
+  constexpr bool plain = std::is_same<Gx, GatherVec<T>>::value;
+  constexpr int MINW = (K == 1 && sizeof(VT) == 4 && plain) ? 1536 / kSellWG : 1;
+  LSPCG_CHECK(K == 1 || spmm_supported(P), LSPCG_ERR_UNSUPPORTED,
+              "SELL launch: no K-vector kernel for view kind " + std::to_string(P.col_bits) + ", block size " +
+                  std::to_string(P.bs));
+  LSPCG_CHECK(plain || P.col_bits != kSellJagX, LSPCG_ERR_UNSUPPORTED,
+              "SELL launch: a SELL-64X view stages a plain vector, not a fused gather");
+  const int64_t grid = sell_grid(P, Epi::NDOT > 0, one_tile_per_wg);
+  if (grid <= 0) return LSPCG_OK;
   const dim3 g{unsigned(grid)}, b{kSellWG};
-  if (P.col_bits == 1) {
-    SdiaArgs<VT> a{P.n, P.ns, P.gp, static_cast<const uint16_t*>(P.col), P.dict, static_cast<const VT*>(vals)};
-    hipLaunchKernelGGL((k_spmm_sdia<T, VT, K, spmm_sb<K>(), kSellWG, Pro, Epi>), g, b, 0, st, a, x, pro, epi);
-  } else if (P.col_bits == 16) {
-    SellArgs<VT, int16_t> a{P.n, P.ns, P.gp, static_cast<const int16_t*>(P.col), P.rowptr, static_cast<const VT*>(vals)};
-    hipLaunchKernelGGL((k_spmm_sell<T, VT, int16_t, K, spmm_qb<K>(), kSellWG, Pro, Epi>), g, b, 0, st, a, x, pro, epi);
-  } else {
-    SellArgs<VT, int32_t> a{P.n, P.ns, P.gp, static_cast<const int32_t*>(P.col), P.rowptr, static_cast<const VT*>(vals)};
-    hipLaunchKernelGGL((k_spmm_sell<T, VT, int32_t, K, spmm_qb<K>(), kSellWG, Pro, Epi>), g, b, 0, st, a, x, pro, epi);
+  if (P.col_bits == kSellDia) {
+    const SdiaArgs<VT> a = sdia_args<VT>(P, vals);
+    if constexpr (K == 1) {
+      if (P.bs == 3) {
+        LSPCG_LAUNCH_SPMV((k_spmv_bsdia3<T, VT, bsdia_sb<VT>(), kSellWG, MINW, Pro, Gx, Epi>), g, b, 0, st, a, pro, gx,
+                          epi);
+        return LSPCG_OK;
+      }
+      LSPCG_LAUNCH_SPMV((k_spmv_sdia<T, VT, kSdiaSB, kSellWG, MINW, Pro, Gx, Epi>), g, b, 0, st, a, pro, gx, epi);
+    } else {
+      LSPCG_LAUNCH_SPMV((k_spmm_sdia<T, VT, K, spmm_sb<K>(), kSellWG, Pro, Epi>), g, b, 0, st, a, gx.x, pro, epi);
+    }
+    return LSPCG_OK;
   }
-  return true;
+  if constexpr (K == 1) {
+    if (P.jagged()) {
+      const SellArgs<VT, int16_t> a = sell_args<VT, int16_t>(P, vals);
+      by_flag(plain && P.col_bits == kSellJagX, [&](auto xs) {
+        constexpr bool XS = plain && decltype(xs)::value;
+        const size_t lds = XS ? size_t(P.kx) * kSellXBlk * sizeof(T) : 0;
+        LSPCG_LAUNCH_SPMV((k_spmv_sellj<T, VT, LSPCG_JAG_QB, kSellWG, MINW, XS, Pro, Gx, Epi>), g, b, lds, st, a, pro,
+                          gx, epi);
+      });
+      return LSPCG_OK;
+    }
+  }
+  // SELL-64 by column word; BSELL-64 (bs 3) has 16-bit offsets or int32 columns
+  auto sell64 = [&](auto ct) {
+    using CT = decltype(ct);
+    const SellArgs<VT, CT> a = sell_args<VT, CT>(P, vals);
+    if constexpr (K == 1 && !std::is_same<CT, uint8_t>::value) {
+      if (P.bs == 3) {
+        LSPCG_LAUNCH_SPMV((k_spmv_bsell3<T, VT, CT, kBsellQB, kSellWG, MINW, Pro, Gx, Epi>), g, b, 0, st, a, pro, gx,
+                          epi);
+        return;
+      }
+    }
+    constexpr int QB = K == 1 ? kSellQB : spmm_qb<K>();
+    LSPCG_LAUNCH_SPMV((k_spmv_sell<T, VT, CT, QB, kSellWG, MINW, Pro, Gx, Epi, K>), g, b, 0, st, a, pro, gx, epi);
+  };
+  if constexpr (K == 1) {
+    if (P.col_bits == kSellCoded) {
+      sell64(uint8_t{});
+      return LSPCG_OK;
+    }
+  }
+  if (P.col_bits == kSellOff16) sell64(int16_t{});
+  else sell64(int32_t{});
+  return LSPCG_OK;
 }
 
 }  // namespace lspcg

@@ -157,13 +157,9 @@ template <typename T, class Gx, class Pro, class Epi>
 int launch_it_gx(lspcg_solver* s, int w, Gx gx, Pro pro, Epi epi, hipStream_t st) {
   if (const SellPattern* P = s->sp[w]) {
     if constexpr (sizeof(T) == 8) {
-      if (s->svd[w] == LSPCG_F32) {
-        launch_spmv_sell_cfg<T, float>(*P, s->sv[w], gx, pro, epi, st);
-        return LSPCG_OK;
-      }
+      if (s->svd[w] == LSPCG_F32) return launch_sell<T, float>(*P, s->sv[w], gx, pro, epi, st);
     }
-    launch_spmv_sell_cfg<T, T>(*P, s->sv[w], gx, pro, epi, st);
-    return LSPCG_OK;
+    return launch_sell<T, T>(*P, s->sv[w], gx, pro, epi, st);
   }
   const lspcg_mat* V = w == 0 ? &s->Av : (w == 1 ? &s->Lv : &s->LTv);
   return launch_spmv_gx<T>(V, gx, pro, epi, st);
@@ -178,12 +174,12 @@ inline CsrView csr_view(const lspcg_solver* s, int w, const lspcg_mat& M) {
   CsrView v{M.rowptr, M.colind, M.vals, M.storage_dtype() == LSPCG_F32 ? 1 : 0, nullptr, nullptr, nullptr, 0, 0};
   if (const SellPattern* P = s->sp[w]) {
     // (SELL-DIA views are never built for systems this kernel solves: build_sell / lspcg_batch_create)
-    if (s->small_sell && s->sv[w] && P->bs == 1 && P->groups > 0 && (P->col_bits == 16 || P->col_bits == 32)) {
+    if (s->small_sell && s->sv[w] && P->bs == 1 && P->groups > 0 && (P->col_bits == kSellOff16 || P->col_bits == kSellInt32)) {
       v.gp = P->gp;
       v.scol = P->col;
       v.sv = s->sv[w];
       v.sf32 = s->svd[w] == LSPCG_F32 ? 1 : 0;
-      v.cmode = P->col_bits == 16 ? 1 : 0;
+      v.cmode = P->col_bits == kSellOff16 ? 1 : 0;
     }
   }
   return v;

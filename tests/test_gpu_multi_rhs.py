@@ -169,24 +169,35 @@ def _rand33():
     return A
 
 
+_SELL64 = {}
+
+
+def _sell64_system(monkeypatch, make, want, max_iter):
+    """The system's solver, its 8 columns and their single solves, built once per system."""
+    if want not in _SELL64:
+        monkeypatch.setenv("LSPCG_REORDER", "0")
+        monkeypatch.setenv("LSPCG_SELLC", "0")
+        A = make()
+        s = _solver(A, _cases.spai_like(A, seed=4))
+        B, X0 = _columns(A, 8)
+        _SELL64[want] = (s, B, X0, _singles(s, B, X0, 1e-8, max_iter))
+    return _SELL64[want]
+
+
+@pytest.mark.parametrize("k", (2, 4, 8))
 @pytest.mark.parametrize("make,want,max_iter", [(_rcm27, "sell16", 0), (_rand33, "sell32", 40)])
-def test_sell64_views(gpu_ctx, monkeypatch, make, want, max_iter):
+def test_sell64_views(gpu_ctx, monkeypatch, make, want, max_iter, k):
     """SELL-64 views with 16-bit offsets (an RCM ordering) and with int32 columns (a random
-    numbering of 35,937 rows: offsets past the 16-bit range; bounded by max_iter = 40)."""
-    monkeypatch.setenv("LSPCG_REORDER", "0")
-    monkeypatch.setenv("LSPCG_SELLC", "0")
-    A = make()
-    L = _cases.spai_like(A, seed=4)
-    s = _solver(A, L)
+    numbering of 35,937 rows: offsets past the 16-bit range; bounded by max_iter = 40), k = 2, 4, 8:
+    the K-vector SELL-64 kernel batches two 4-entry groups at K = 2 and one at K = 4, 8."""
+    s, B, X0, singles = _sell64_system(monkeypatch, make, want, max_iter)
     views = s.views
     assert [views[m]["columns"] for m in ("A", "L", "LT")] == [want] * 3, views
-    B, X0 = _columns(A, 4)
-    singles = _singles(s, B, X0, 1e-8, max_iter)
-    res, X = _multi(s, B, X0, 1e-8, max_iter)
+    res, X = _multi(s, B[:, :k].copy(), X0[:, :k].copy(), 1e-8, max_iter)
     if max_iter:
-        assert [r[0] for r in res] == [40, 40, 0, 0] and len(res[0][2]) == 41
-    same = _check(res, X, singles, what=want)
-    print(f"{want}: columns bit-identical to their single solves: {same}/4")
+        assert [r[0] for r in res][:4] == [40, 40, 0, 0][:k] and len(res[0][2]) == 41
+    same = _check(res, X, singles[:k], what=f"{want} k={k}")
+    print(f"{want} k={k}: columns bit-identical to their single solves: {same}/{k}")
 
 
 @pytest.fixture(scope="module")

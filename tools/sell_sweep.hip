@@ -271,7 +271,7 @@ const Cfg kCfgs[] = {
 template <typename VT, int QB, int MINW>
 void launch_bsr(const SellPattern& P, const void* vals, const double* x, double* y, hipStream_t st) {
   const int64_t grid = (P.nb + kSellWG - 1) / kSellWG;
-  SellArgs<VT, int16_t> a{P.n, P.ns, P.gp, static_cast<const int16_t*>(P.col), P.rowptr, static_cast<const VT*>(vals)};
+  const SellArgs<VT, int16_t> a = sell_args<VT, int16_t>(P, vals);
   hipLaunchKernelGGL((k_spmv_bsell3<double, VT, int16_t, QB, kSellWG, MINW, ProNone, GatherVec<double>, EpiStore<double>>),
                      dim3(unsigned(grid)), dim3(kSellWG), 0, st, a, ProNone{}, GatherVec<double>{x}, EpiStore<double>{y});
 }
