@@ -3,9 +3,10 @@
 ``tests/golden/factor_bits.json`` holds the sha256 of ``ic0()``, ``ainv0()`` (indptr, indices and
 data bytes) and of ``trsv(lower=True)`` / ``trsv(lower=False)`` on the device's own IC(0) factor and
 its sorted transpose, for the masked ``poisson2d_grid(16, 16)`` and ``kuhn_dirichlet(7)`` of
-``test_gpu_precond._systems``.  The oracle is fp64 only, so nothing else runs ``k_ic0_level<float>``,
-``k_ainv_*<float>`` or ``k_trsv_syncfree<float, *>`` (with its own NaN wait pattern); the fp64
-digests are a second guard beside ``test_gpu_precond``'s comparison with the oracle.  A few hundred
+``test_gpu_precond._systems``.  The oracle reproduces every digest in both precisions
+(``tests/test_factor_host.py``, on the CPU), so these are a second guard beside the comparisons with
+the oracle in ``test_gpu_precond`` (fp64, grids) and ``test_gpu_factor_shapes`` (fp32 and fp64,
+irregular matrices).  A few hundred
 rows in tens of levels: the padded order spans several 256-position blocks, so several workgroups
 of the sync-free solve wait on one another.
 
@@ -55,17 +56,20 @@ def sha_csr(M):
     return sha(M.indptr.astype(np.int32), M.indices.astype(np.int32), M.data)
 
 
-def oracle_bits(name):
-    """The same record from oracle/precond.py (fp64 only)."""
+def oracle_bits(name, dt="f64"):
+    """The same record from oracle/precond.py in that precision (tests/test_factor_host.py holds
+    it to the fixture in both, without a GPU)."""
     from oracle import precond as OP
 
+    npdt = DTYPES[dt]
     A = systems()[name][0]
-    L = OP.ic0(A)
+    L = OP.ic0(A, npdt)
     U = sp.csr_matrix(L.T)
     U.sort_indices()
-    r = np.random.default_rng(3).normal(size=A.shape[0])
-    return {"ic0": sha_csr(L), "ainv0": sha_csr(OP.ainv_spai_factor(A)), "trsv_lower": sha(OP.trsv_lower(L, r)),
-            "trsv_upper": sha(OP.trsv_upper(U, r))}
+    r = np.random.default_rng(3).normal(size=A.shape[0]).astype(npdt)
+    y, z = OP.trsv_lower(L, r, npdt), OP.trsv_upper(U, r, npdt)
+    assert L.data.dtype == npdt and y.dtype == npdt and z.dtype == npdt
+    return {"ic0": sha_csr(L), "ainv0": sha_csr(OP.ainv_spai_factor(A, npdt)), "trsv_lower": sha(y), "trsv_upper": sha(z)}
 
 
 def bits(name, dt):
