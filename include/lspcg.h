@@ -190,6 +190,15 @@ int lspcg_solver_set_ic_factor(lspcg_solver* s, const lspcg_mat* L, double* t_pr
  * run the whole loop in one single-workgroup launch -- same bits as the multi-kernel schedule. */
 int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int64_t max_iter,
                        int64_t* iters, double* res_hist, double* t_solve_ms);
+/* lspcg_solver_solve that also records the loop's scalars: coef (host, nullable, 2*(max_iter+1)
+ * doubles) receives the `iters` pairs coef[2k] = rho_k = r_k.z_k, coef[2k+1] = pi_k = p_k.q_k -- the
+ * rounded values the recurrence itself divides for alpha_k, stored by the thread that commits
+ * iteration k, in every schedule, preconditioner kind, dtype and dot order.  They are the Lanczos
+ * coefficients of M^-1 A (lspcg_cg_lanczos).  A solve stopped by a non-finite residual reports
+ * max_iter iterations and NaN for the pairs it did not complete.  coef == NULL is
+ * lspcg_solver_solve: the same launches, the same bits in x, iters and res_hist. */
+int lspcg_solver_solve_coef(lspcg_solver* s, const void* b, void* x, double rtol, int64_t max_iter,
+                            int64_t* iters, double* res_hist, double* t_solve_ms, double* coef);
 /* Solve A X = B for nrhs = 1..8 right-hand sides of the one system in one lockstep loop (heat time
  * steps on a fixed mesh, load cases, a repeated sample).  B, X: device arrays
  * [n][nrhs], row-major and contiguous, of the solver's dtype; X holds x0 on entry and the
@@ -276,7 +285,27 @@ int lspcg_batch_create_precond(lspcg_ctx* ctx, int nsys, const lspcg_mat* const*
  * t_solve_ms = device time of the whole batch.  Returns LSPCG_OK when every system converged. */
 int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, double rtol, int64_t max_iter,
                       int64_t* iters, int32_t* status, double* const* res_hist, double* t_solve_ms);
+/* lspcg_batch_solve that also records every system's (rho_k, pi_k) pairs as lspcg_solver_solve_coef
+ * does: coef (nullable) holds per-system host arrays of 2*(max_iter_k+1) doubles (or NULL entries). */
+int lspcg_batch_solve_coef(lspcg_batch* bt, const void* const* b, void* const* x, double rtol, int64_t max_iter,
+                           int64_t* iters, int32_t* status, double* const* res_hist, double* t_solve_ms,
+                           double* const* coef);
 int lspcg_batch_destroy(lspcg_batch* bt);
+
+/* ---- spectrum of the preconditioned system from the PCG scalars (host only: no device call) ----
+ * CG is Lanczos on M^-1 A: with alpha_k = rho_k/pi_k and beta_k = rho_k/rho_{k-1}, the m recorded
+ * pairs give the m x m tridiagonal T_m whose extreme eigenvalues (Ritz values) converge to those of
+ * M^-1 A as the solve converges (Golub & Van Loan, Matrix Computations, sec. 11.3; Saad, Iterative
+ * Methods for Sparse Linear Systems, sec. 6.7; PETSc's KSPComputeExtremeSingularValues on its CG).
+ * lspcg_cg_lanczos: diag[0] = pi_0/rho_0, diag[k] = pi_k/rho_k + (rho_k/rho_{k-1}) pi_{k-1}/rho_{k-1},
+ * off[k] = sqrt(rho_{k+1}/rho_k) pi_k/rho_k for k < m-1 (diag: m doubles, off: m-1, may be NULL for
+ * m == 1).  LSPCG_ERR_ARG for m < 1, a NULL array, or a rho / pi that is not positive and finite (a
+ * breakdown, or an operator that is not SPD): never a silent NaN. */
+int lspcg_cg_lanczos(int64_t m, const double* coef, double* diag, double* off);
+/* Smallest and largest eigenvalue of the symmetric tridiagonal (diag[m], off[m-1]): Sturm-count
+ * bisection of the Gershgorin interval in double, down to adjacent doubles.  LSPCG_ERR_ARG for
+ * m < 1, a NULL array or a non-finite entry. */
+int lspcg_tridiag_extremes(int64_t m, const double* diag, const double* off, double* lmin, double* lmax);
 
 /* ---- CSR assembly with Dirichlet masking (to_csr_cpu on device) ----
  * edge_index: device int64 [2,E] (row-major sorted, duplicate free -- checked);

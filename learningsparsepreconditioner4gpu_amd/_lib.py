@@ -71,6 +71,7 @@ SIGNATURES = {
     "lspcg_solver_set_ic": (C.c_int, [vp, p_f64]),
     "lspcg_solver_set_ic_factor": (C.c_int, [vp, vp, p_f64]),
     "lspcg_solver_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_int64, p_i64, p_f64, p_f64]),
+    "lspcg_solver_solve_coef": (C.c_int, [vp, vp, vp, C.c_double, C.c_int64, p_i64, p_f64, p_f64, p_f64]),
     "lspcg_solver_solve_multi": (C.c_int, [vp, C.c_int, vp, vp, C.c_double, C.c_int64, p_i64, p_i32,
                                           C.POINTER(p_f64), p_f64]),
     "lspcg_solver_time_kernels": (C.c_int, [vp, vp, C.c_int64, p_f64, C.POINTER(C.c_int)]),
@@ -81,7 +82,11 @@ SIGNATURES = {
     "lspcg_batch_create": (C.c_int, [vp, C.c_int, pp, pp, C.c_double, pp]),
     "lspcg_batch_create_precond": (C.c_int, [vp, C.c_int, pp, pp, C.c_int, C.c_double, pp]),
     "lspcg_batch_solve": (C.c_int, [vp, pp, pp, C.c_double, C.c_int64, p_i64, p_i32, C.POINTER(p_f64), p_f64]),
+    "lspcg_batch_solve_coef": (C.c_int, [vp, pp, pp, C.c_double, C.c_int64, p_i64, p_i32, C.POINTER(p_f64), p_f64,
+                                        C.POINTER(p_f64)]),
     "lspcg_batch_destroy": (C.c_int, [vp]),
+    "lspcg_cg_lanczos": (C.c_int, [C.c_int64, p_f64, p_f64, p_f64]),
+    "lspcg_tridiag_extremes": (C.c_int, [C.c_int64, p_f64, p_f64, p_f64, p_f64]),
     "lspcg_assemble": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int,
                                  C.c_int, pp]),
     "lspcg_gnn_create": (C.c_int, [vp, C.POINTER(lspcg_gnn_desc), vp, C.c_int64, pp]),

@@ -170,7 +170,8 @@ struct EpiQB : RowQ<T>, BySystem {
   __device__ __forceinline__ void finish(DD (&dd)[1]) const { finish_by_system(*this, dd); }
   __device__ static __forceinline__ void fin(PcgState* St, const double* v) {
     const int64_t k = St->iter;
-    keep_q<T, true>(St, k, St->rho, v[0]);
+    double* const coef = St->coef;
+    keep_q<T, true>(St, k, coef, St->rho, v[0]);
   }
 };
 
@@ -328,7 +329,8 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r_sums(BatchMap m, Pc
   if (int64_t(blockIdx.x) == int64_t(t0) * m.bs && threadIdx.x == 0) {
     const double rho_old = St->rho;
     const int64_t k = St->iter;
-    commit_step<T>(St, rho_old, rho, pq, alpha, k + 1);
+    double* const coef = St->coef;
+    commit_step<T>(St, coef, rho_old, rho, pq, alpha, k + 1);
   }
   r[i] = ri - alpha * qi;
 }
@@ -358,7 +360,8 @@ __global__ void __launch_bounds__(kThreads) k_batch_update_r_sums_cg(BatchMap m,
   if (int64_t(blockIdx.x) == int64_t(t0) * m.bs && threadIdx.x == 0) {
     const double rho_old = St->rho;
     const int64_t k = St->iter;
-    commit_step<T>(St, rho_old, rho, pq, alpha, k + 1);
+    double* const coef = St->coef;
+    commit_step<T>(St, coef, rho_old, rho, pq, alpha, k + 1);
   }
   DD dots[ND];
 #pragma unroll
@@ -743,6 +746,12 @@ int lspcg_batch_create_precond(lspcg_ctx* ctx, int nsys, const lspcg_mat* const*
 
 int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, double rtol, int64_t max_iter,
                       int64_t* iters, int32_t* status, double* const* res_hist, double* t_solve_ms) {
+  return lspcg_batch_solve_coef(bt, b, x, rtol, max_iter, iters, status, res_hist, t_solve_ms, nullptr);
+}
+
+int lspcg_batch_solve_coef(lspcg_batch* bt, const void* const* b, void* const* x, double rtol, int64_t max_iter,
+                           int64_t* iters, int32_t* status, double* const* res_hist, double* t_solve_ms,
+                           double* const* coef) {
   LSPCG_CHECK(bt && b && x && iters && status, LSPCG_ERR_ARG, "batch_solve: NULL argument");
   const int ns = bt->nsys;
   for (int k = 0; k < ns; ++k) LSPCG_CHECK(b[k] && x[k], LSPCG_ERR_ARG, "batch_solve: NULL vector " + std::to_string(k));
@@ -750,12 +759,15 @@ int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, dou
   LSPCG_HIP(hipSetDevice(bt->ctx->device));
   hipStream_t st = s->stream;
   const size_t es = esize(bt->dtype);
-  std::vector<int64_t> mi(ns), hoff(ns + 1, 0);
+  std::vector<int64_t> mi(ns), hoff(ns + 1, 0), coff(ns + 1, 0);
   for (int k = 0; k < ns; ++k) {
     mi[k] = max_iter > 0 ? max_iter : bt->n[k];
     hoff[k + 1] = hoff[k] + ((res_hist && res_hist[k]) ? mi[k] + 2 : 0);
   }
-  if (int rc = grow_hist(&bt->dhist, &bt->dhist_cap, hoff[ns], st)) return rc;
+  // the recorded (ρ_k, π_k) pairs follow the histories in the same buffer, at even offsets (16-B stores)
+  coff[0] = (hoff[ns] + 1) / 2 * 2;
+  for (int k = 0; k < ns; ++k) coff[k + 1] = coff[k] + ((coef && coef[k]) ? 2 * (mi[k] + 1) : 0);
+  if (int rc = grow_hist(&bt->dhist, &bt->dhist_cap, coff[ns], st)) return rc;
   std::unique_lock<std::mutex> sub(submit_mutex());  // as in lspcg_solver_solve
   LSPCG_HIP(hipEventRecord(s->ev_in, bt->ctx->stream));
   LSPCG_HIP(hipStreamWaitEvent(st, s->ev_in, 0));
@@ -767,7 +779,8 @@ int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, dou
     LSPCG_HIP(hipMemcpyAsync(cx + es * bt->off[k], x[k], es * bt->n[k], hipMemcpyDeviceToDevice, st));
   }
   for (int k = 0; k < ns; ++k)
-    bt->hS[k] = initial_state(rtol, s->eps, (res_hist && res_hist[k]) ? bt->dhist + hoff[k] : nullptr, mi[k]);
+    bt->hS[k] = initial_state(rtol, s->eps, (res_hist && res_hist[k]) ? bt->dhist + hoff[k] : nullptr, mi[k],
+                              (coef && coef[k]) ? bt->dhist + coff[k] : nullptr);
   LSPCG_HIP(hipMemcpyAsync(bt->S, bt->hS, sizeof(PcgState) * ns, hipMemcpyHostToDevice, st));
   int rc = by_dtype(bt->dtype, [&](auto t) { return enqueue_batch_init<decltype(t)>(bt, st); });
   if (rc) return rc;
@@ -804,7 +817,7 @@ int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, dou
   float ms = 0.f;
   LSPCG_HIP(hipEventElapsedTime(&ms, s->ev_t0, s->ev_t1));
   if (t_solve_ms) *t_solve_ms = ms;
-  return report_states(ns, cur.data(), mi.data(), bt->dhist, hoff.data(), iters, status, res_hist);
+  return report_states(ns, cur.data(), mi.data(), bt->dhist, hoff.data(), iters, status, res_hist, coff.data(), coef);
 }
 
 }  // extern "C"

@@ -136,7 +136,7 @@ struct EpiQK {
     for (int k = 0; k < K; ++k) done[k] = S[k].done, it[k] = S[k].iter, rho[k] = S[k].rho;
 #pragma unroll
     for (int k = 0; k < K; ++k)
-      if (!done[k]) keep_q<T, true>(S + k, it[k], rho[k], v[k]);
+      if (!done[k]) keep_q<T, true>(S + k, it[k], nullptr, rho[k], v[k]);
   }
 };
 

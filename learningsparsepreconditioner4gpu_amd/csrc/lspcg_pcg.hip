@@ -317,7 +317,8 @@ static int enqueue_iteration(lspcg_solver* s, hipStream_t st) {
   rc = spai ? launch_it<T>(s, 0, p, ProDone{S}, EpiQ<T, true>{{q, p}, last}, st)
             : launch_it<T>(s, 0, p, ProDone{S}, EpiQ<T>{{q, p}, last}, st);
   if (rc) return rc;
-  enqueue_ob<kObQ>(s, st, 1, p, q);
+  if (spai) enqueue_ob<kObQ, false, true>(s, st, 1, p, q);  // (EpiQ<T, true> has counted the iteration)
+  else enqueue_ob<kObQ>(s, st, 1, p, q);
   switch (s->precond) {
     case LSPCG_PRECOND_EXT_SPAI:
     case LSPCG_PRECOND_EXT_SPAI_SCALED: launch(k_update_r_nodot<T>, eg, eb, st, n, S, q, r); break;
@@ -675,6 +676,11 @@ int lspcg_solver_set_ic_factor(lspcg_solver* s, const lspcg_mat* L, double* t_pr
 
 int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int64_t max_iter, int64_t* iters,
                        double* res_hist, double* t_solve_ms) {
+  return lspcg_solver_solve_coef(s, b, x, rtol, max_iter, iters, res_hist, t_solve_ms, nullptr);
+}
+
+int lspcg_solver_solve_coef(lspcg_solver* s, const void* b, void* x, double rtol, int64_t max_iter, int64_t* iters,
+                            double* res_hist, double* t_solve_ms, double* coef) {
   LSPCG_CHECK(s && b && x && iters, LSPCG_ERR_ARG, "solve: NULL argument");
   LSPCG_CHECK(!(s->precond == LSPCG_PRECOND_EXT_SPAI || s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED) || s->LT,
               LSPCG_ERR_ARG, "solve: ext_spai not set");
@@ -699,6 +705,21 @@ int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int
     }
     dhist = s->dhist;
   }
+  double* dcoef = nullptr;  // the recorded (ρ_k, π_k) pairs: the same handling
+  if (coef) {
+    if (s->dcoef_cap < 2 * (max_iter + 1)) {
+      LSPCG_HIP(hipStreamSynchronize(st));
+      (void)hipFree(s->dcoef);
+      (void)hipHostFree(s->hcoef);
+      s->dcoef = nullptr;
+      s->hcoef = nullptr;
+      s->dcoef_cap = 0;
+      LSPCG_HIP(hipMalloc(&s->dcoef, sizeof(double) * 2 * (max_iter + 1)));
+      LSPCG_HIP(hipHostMalloc(&s->hcoef, sizeof(double) * 2 * (max_iter + 1), hipHostMallocDefault));
+      s->dcoef_cap = 2 * (max_iter + 1);
+    }
+    dcoef = s->dcoef;
+  }
 
   // every enqueue below runs under the process-wide submission lock, released around each host
   // wait (lspcg_internal.hpp: concurrent solves from several host threads)
@@ -714,7 +735,7 @@ int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int
     LSPCG_HIP(hipMemcpyAsync(s->b, b, vb, hipMemcpyDeviceToDevice, st));
     LSPCG_HIP(hipMemcpyAsync(s->x, x, vb, hipMemcpyDeviceToDevice, st));
   }
-  *s->hS = initial_state(rtol, s->eps, dhist, max_iter);
+  *s->hS = initial_state(rtol, s->eps, dhist, max_iter, dcoef);
   LSPCG_HIP(hipMemcpyAsync(s->S, s->hS, sizeof(PcgState), hipMemcpyHostToDevice, st));
   int rc = by_dtype(s->dtype, [&](auto t) { return enqueue_init<decltype(t)>(s, st); });
   if (rc) return rc;
@@ -758,6 +779,8 @@ int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int
   }
   const SolveTail tail(fin, max_iter);
   if (res_hist) LSPCG_HIP(hipMemcpyAsync(s->hhist, dhist, sizeof(double) * tail.written, hipMemcpyDeviceToHost, st));
+  if (coef && tail.pairs() > 0)
+    LSPCG_HIP(hipMemcpyAsync(s->hcoef, dcoef, sizeof(double) * 2 * tail.pairs(), hipMemcpyDeviceToHost, st));
   LSPCG_HIP(hipEventRecord(s->ev_out, st));
   LSPCG_HIP(hipStreamWaitEvent(s->ctx->stream, s->ev_out, 0));
   sub.unlock();
@@ -782,6 +805,10 @@ int lspcg_solver_solve(lspcg_solver* s, const void* b, void* x, double rtol, int
   if (res_hist) {
     std::memcpy(res_hist, s->hhist, sizeof(double) * tail.written);
     tail.nan_fill(res_hist);
+  }
+  if (coef) {
+    std::memcpy(coef, s->hcoef, sizeof(double) * 2 * tail.pairs());
+    tail.nan_fill_coef(coef);
   }
   return (fin.done == 1) ? LSPCG_OK : LSPCG_NOT_CONVERGED;
 }
@@ -920,6 +947,8 @@ int lspcg_solver_destroy(lspcg_solver* s) {
   (void)hipFree(s->ob_part);
   (void)hipFree(s->dhist);
   (void)hipHostFree(s->hhist);
+  (void)hipFree(s->dcoef);
+  (void)hipHostFree(s->hcoef);
   (void)hipHostFree(s->hflags);
   (void)hipStreamDestroy(s->stream);
   delete s;

@@ -162,8 +162,10 @@ struct EpiZ : RowZ<T, SCALED>, ByLastArriver {
 template <typename T, bool INC = false>
 struct EpiQ : RowQ<T>, ByLastArriver {
   __device__ __forceinline__ void fin(const double* v) const {
-    const int64_t k = INC ? S->iter : 0;
-    keep_q<T, INC>(S, k, S->rho, v[0]);
+    double* const coef = S->coef;
+    // not INC: the r update counts the iteration after this launch, and only a recorded pair needs k
+    const int64_t k = (INC || coef) ? S->iter : 0;
+    keep_q<T, INC>(S, k, coef, S->rho, v[0]);
   }
 };
 
@@ -435,12 +437,13 @@ __global__ void __launch_bounds__(kThreads) k_update_r_g(int64_t n, PcgState* S,
   const int64_t k = S->iter;
   const double rho_prev = S->rho;
   const double rho = S->rho_k;
+  double* const coef = S->coef;
   double vq[1];
   group_sum_dd<1>(gq, ngq, vq);
   if (done) return;
   const double pq = round_to<T>(vq[0]);
   const T alpha = T(rho) / T(pq);
-  if (blockIdx.x == 0 && threadIdx.x == 0) commit_step<T>(S, rho_prev, rho, pq, alpha, k + 1);
+  if (blockIdx.x == 0 && threadIdx.x == 0) commit_step<T>(S, coef, rho_prev, rho, pq, alpha, k + 1);
   for (int64_t j0 = jt; j0 < nv; j0 += ts * kElemUnroll) {
     if (j0 != jt) load(j0);
 #pragma unroll
@@ -483,12 +486,13 @@ __global__ void __launch_bounds__(kThreads) k_update_r_gd(int64_t n, PcgState* S
   const int64_t k = S->iter;
   const double rho_prev = S->rho;
   const double rho = S->rho_k;
+  double* const coef = S->coef;
   double vq[1];
   group_sum_dd<1>(gq, ngq, vq);
   if (done) return;  // uniform: UP exits too, nobody reads the groups
   const double pq = round_to<T>(vq[0]);
   const T alpha = T(rho) / T(pq);
-  if (blockIdx.x == 0 && threadIdx.x == 0) commit_step<T>(S, rho_prev, rho, pq, alpha, k + 1);
+  if (blockIdx.x == 0 && threadIdx.x == 0) commit_step<T>(S, coef, rho_prev, rho, pq, alpha, k + 1);
   DD dots[2] = {dd_zero(), dd_zero()};  // ρ_{k+1}, ‖r_{k+1}‖²
   auto elem = [&](T ri, int64_t i) { r_dots_row<T, PRE, true>(i, ri, d, z, dots[1], dots[0]); };
   for (int64_t j0 = jt; j0 < nv; j0 += ts * kElemUnroll) {
@@ -669,6 +673,7 @@ __global__ void __launch_bounds__(TH) k_pcg_small(int32_t n, PcgState* S, CsrVie
   const double atol = S->atol;
   const int64_t max_iter = S->max_iter;
   double* hist = S->hist;
+  double* const coef = S->coef;
   const double rr0 = S->rr;
   double rho_prev = S->rho, rho = S->rho, pq = S->pq;
   T alpha = T(S->alpha);
@@ -758,6 +763,7 @@ __global__ void __launch_bounds__(TH) k_pcg_small(int32_t n, PcgState* S, CsrVie
     small_dots<T, 1, TH>(dq, lds_q, v1);
     pq = v1[0];
     alpha = T(rho) / T(pq);
+    if (tid == 0) keep_coef(coef, k, rho, pq);
 #pragma unroll
     for (int m = 0; m < R; ++m) {
       rr_[m] = rr_[m] - alpha * qr[m];
@@ -772,7 +778,7 @@ __global__ void __launch_bounds__(TH) k_pcg_small(int32_t n, PcgState* S, CsrVie
     p[off + row[m]] = pr[m];
   }
   if (tid == 0) {
-    commit_step<T>(S, rho_prev, rho, pq, alpha, k);
+    commit_step<T>(S, nullptr, rho_prev, rho, pq, alpha, k);
     S->done = code;
   }
 }

@@ -135,12 +135,14 @@ enum ObWhich { kObInit = 0, kObZ = 1, kObQ = 2, kObR = 3, kObRho = 4, kObRR = 5 
 // up to 3 dots (xs[j] · ys[j]); thread 0 then writes the scalars of phase WHICH:
 //   kObInit  rr = r·r, bb = b·b, atol, rho = (DIAG ? r·z : rr), done (‖b‖ = 0), hist[0]
 //   kObZ     rho = r·z ; rr = r·r and hist[k] for k > 0           (after KB's EpiZ)
-//   kObQ     pq = p·q ; alpha = rho / pq                           (after KC's EpiQ)
+//   kObQ     pq = p·q ; alpha = rho / pq ; the recorded (rho, pq)  (after KC's EpiQ, whose pair it rewrites)
 //   kObR     rr = r·r ; rho = (DIAG ? r·z : rr) ; hist[k]           (after CG / Jacobi k_update_r)
 //   kObRho   rho = r·z                                             (after IC's k_dot_rho)
 //   kObRR    rr = r·r ; hist[k]                                    (after IC's k_update_r)
 // thread 0's scalar update of phase WHICH from the dot values v[0..nd)
-template <int WHICH, bool DIAG>
+// COUNTED (kObQ only): KC's EpiQ has already counted the iteration (ext_spai), so the pair recorded
+// here is iteration S->iter - 1's
+template <int WHICH, bool DIAG, bool COUNTED = false>
 __device__ __forceinline__ void ob_epilogue(PcgState* S, const double (&v)[3]) {
   const int64_t k = S->iter;
   if constexpr (WHICH == kObInit) {
@@ -158,8 +160,11 @@ __device__ __forceinline__ void ob_epilogue(PcgState* S, const double (&v)[3]) {
       if (S->hist) S->hist[k] = sqrt(v[1]);
     }
   } else if constexpr (WHICH == kObQ) {
+    const double rho = S->rho;
+    double* const coef = S->coef;
     S->pq = v[0];
-    S->alpha = S->rho / v[0];
+    S->alpha = rho / v[0];
+    keep_coef(coef, COUNTED ? k - 1 : k, rho, v[0]);
   } else if constexpr (WHICH == kObR) {
     S->rr = v[0];
     S->rho = DIAG ? v[1] : v[0];
@@ -182,7 +187,7 @@ __device__ __forceinline__ void ob_join(const double* part, int nd, int ch, doub
   }
 }
 
-template <int WHICH, bool DIAG>
+template <int WHICH, bool DIAG, bool COUNTED = false>
 __global__ void __launch_bounds__(kObBlock) k_dot_openblas(int64_t n, int nch, int nd, PcgState* S, const double* x0,
                                                            const double* y0, const double* x1, const double* y1,
                                                            const double* x2, const double* y2) {
@@ -205,7 +210,7 @@ __global__ void __launch_bounds__(kObBlock) k_dot_openblas(int64_t n, int nch, i
   if (threadIdx.x != 0) return;
   double v[3];
   ob_join(part, nd, ch, v);
-  ob_epilogue<WHICH, DIAG>(S, v);
+  ob_epilogue<WHICH, DIAG, COUNTED>(S, v);
 }
 
 // Large n (>= kObSplitN): one single-wave workgroup per (dot, chunk) item -- every chunk of every
@@ -229,17 +234,17 @@ __global__ void __launch_bounds__(64) k_dot_openblas_item(int64_t n, int nch, co
   if (threadIdx.x == 0) part[j * kObMaxThreads + c] = v;
 }
 
-template <int WHICH, bool DIAG>
+template <int WHICH, bool DIAG, bool COUNTED = false>
 __global__ void k_dot_openblas_fin(int64_t n, int nch, int nd, PcgState* S, const double* part) {
   if (threadIdx.x != 0 || (WHICH != kObInit && S->done)) return;
   const int ch = (n > 10000 && nch > 1) ? nch : 1;
   double v[3];
   ob_join(part, nd, ch, v);
-  ob_epilogue<WHICH, DIAG>(S, v);
+  ob_epilogue<WHICH, DIAG, COUNTED>(S, v);
 }
 
 // parity mode: every reducing launch is followed by k_dot_openblas, which rewrites its scalars
-template <int WHICH, bool DIAG = false>
+template <int WHICH, bool DIAG = false, bool COUNTED = false>
 static void enqueue_ob(lspcg_solver* s, hipStream_t st, int nd, const void* x0, const void* y0,
                        const void* x1 = nullptr, const void* y1 = nullptr, const void* x2 = nullptr,
                        const void* y2 = nullptr) {
@@ -254,12 +259,12 @@ static void enqueue_ob(lspcg_solver* s, hipStream_t st, int nd, const void* x0, 
   if (s->n >= kObSplitN) {  // large n: one CU per (dot, chunk), then the ordered join
     hipLaunchKernelGGL(k_dot_openblas_item<WHICH>, dim3(nd * ch), dim3(64), 0, st, s->n, s->dot_threads, s->S,
                        s->ob_part, X0, Y0, X1, Y1, X2, Y2);
-    hipLaunchKernelGGL((k_dot_openblas_fin<WHICH, DIAG>), dim3(1), dim3(64), 0, st, s->n, s->dot_threads, nd, s->S,
+    hipLaunchKernelGGL((k_dot_openblas_fin<WHICH, DIAG, COUNTED>), dim3(1), dim3(64), 0, st, s->n, s->dot_threads, nd, s->S,
                        static_cast<const double*>(s->ob_part));
     return;
   }
   const int waves = std::min(kObBlock / 64, std::max(1, nd * ch));
-  hipLaunchKernelGGL((k_dot_openblas<WHICH, DIAG>), dim3(1), dim3(64 * waves), 0, st, s->n, s->dot_threads, nd, s->S,
+  hipLaunchKernelGGL((k_dot_openblas<WHICH, DIAG, COUNTED>), dim3(1), dim3(64 * waves), 0, st, s->n, s->dot_threads, nd, s->S,
                      X0, Y0, X1, Y1, X2, Y2);
 }
 

@@ -23,6 +23,7 @@ struct PcgState {
   double rtol;
   double eps;       // ε of ext_spai
   double* hist;     // ‖r_k‖ history (nullable)
+  double* coef;     // (ρ_k, π_k) of every completed iteration, the CG-Lanczos coefficients (nullable, 16-B aligned)
   int64_t iter;     // completed iterations
   int64_t max_iter;
   int32_t done;     // 0 running, 1 converged, 2 max_iter reached, 3 non-finite residual
@@ -92,12 +93,20 @@ __device__ __forceinline__ double keep_z(PcgState* St, int64_t k, double rho_old
   return rr;
 }
 
-// KC's keep: π_k, α_k = ρ_k/π_k in T and (INC: this launch completes iteration k) the count
+// The pair (ρ_k, π_k) of iteration k as the recurrence uses it -- the rounded values that give α_k --
+// in one 16-byte store; nothing without a buffer.
+__device__ __forceinline__ void keep_coef(double* coef, int64_t k, double rho, double pq) {
+  if (coef) *reinterpret_cast<double2*>(coef + 2 * k) = make_double2(rho, pq);
+}
+
+// KC's keep: π_k, α_k = ρ_k/π_k in T, the recorded pair and (INC: this launch completes iteration k)
+// the count
 template <typename T, bool INC>
-__device__ __forceinline__ void keep_q(PcgState* St, int64_t k, double rho, double pq_sum) {
+__device__ __forceinline__ void keep_q(PcgState* St, int64_t k, double* coef, double rho, double pq_sum) {
   const double pq = round_to<T>(pq_sum);
   St->pq = pq;
   St->alpha = double(T(rho) / T(pq));
+  keep_coef(coef, k, rho, pq);
   if constexpr (INC) St->iter = k + 1;
 }
 
@@ -117,10 +126,12 @@ __device__ __forceinline__ double keep_r(PcgState* St, int64_t it, double rho_ol
   return rr;
 }
 
-// the consumer-summing UR's (and the one-workgroup solve's) commit of a finished iteration
+// the consumer-summing UR's commit of a finished iteration, iter - 1, with its recorded pair (the
+// one-workgroup solve commits once, after its loop, and records inside it: coef = nullptr here)
 template <typename T>
-__device__ __forceinline__ void commit_step(PcgState* St, double rho_prev, double rho, double pq, T alpha,
-                                            int64_t iter) {
+__device__ __forceinline__ void commit_step(PcgState* St, double* coef, double rho_prev, double rho, double pq,
+                                            T alpha, int64_t iter) {
+  keep_coef(coef, iter - 1, rho, pq);
   St->rho_prev = rho_prev;
   St->rho = rho;
   St->pq = pq;

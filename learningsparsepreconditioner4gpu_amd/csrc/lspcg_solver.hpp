@@ -129,6 +129,9 @@ struct lspcg_solver {
   double* dhist = nullptr;  // device residual history (lspcg_solver_solve with res_hist), grown on demand
   double* hhist = nullptr;  // its pinned host mirror (the history's copy is enqueued, not a blocking copy)
   int64_t dhist_cap = 0;
+  double* dcoef = nullptr;  // device (ρ_k, π_k) pairs (lspcg_solver_solve_coef with coef), grown on demand
+  double* hcoef = nullptr;  // their pinned host mirror
+  int64_t dcoef_cap = 0;
   unsigned* hflags = nullptr;  // pinned: the IC triangular solves' timeout flags, copied behind the solve
   int64_t small_n = lspcg::kSmallNDefault;  // largest n solved by k_pcg_small (LSPCG_SMALL_N; 0 disables it; also bounded by
                            // 3 rows per thread at 1024 threads and the LDS of 3 vectors: 2560 in fp64)
@@ -230,9 +233,9 @@ int launch_pcg_small(int precond, int grid, lspcg_solver* s, int64_t n, PcgState
 }
 
 // The state a solve starts from (the init launch adds the norms and atol).
-inline PcgState initial_state(double rtol, double eps, double* hist, int64_t max_iter) {
+inline PcgState initial_state(double rtol, double eps, double* hist, int64_t max_iter, double* coef = nullptr) {
   PcgState init{};
-  init.rtol = rtol, init.eps = eps, init.hist = hist, init.max_iter = max_iter;
+  init.rtol = rtol, init.eps = eps, init.hist = hist, init.coef = coef, init.max_iter = max_iter;
   return init;
 }
 
@@ -244,6 +247,10 @@ struct SolveTail {
       : iters(fin.done == 3 ? max_iter : fin.iter), written(std::min<int64_t>(fin.iter, max_iter) + 1) {}
   void nan_fill(double* hist) const {  // ... so the rest of 0..iters is NaN-filled
     for (int64_t k = written; k <= iters; ++k) hist[k] = NAN;
+  }
+  int64_t pairs() const { return written - 1; }  // (ρ_k, π_k) of the completed iterations were recorded ...
+  void nan_fill_coef(double* coef) const {       // ... so the rest of the `iters` pairs is NaN-filled
+    for (int64_t k = 2 * pairs(); k < 2 * iters; ++k) coef[k] = NAN;
   }
 };
 
@@ -260,10 +267,12 @@ inline int grow_hist(double** buf, int64_t* cap, int64_t need, hipStream_t st) {
   return LSPCG_OK;
 }
 
-// iters / status / res_hist (nullable, entries nullable) of ns systems from their final states,
-// system k's history at dhist + hoff[k]; LSPCG_OK when every system converged
+// iters / status / res_hist / coef (nullable, entries nullable) of ns systems from their final
+// states, system k's history at dhist + hoff[k], its recorded pairs at dhist + coff[k]; LSPCG_OK when
+// every system converged
 inline int report_states(int ns, const PcgState* fin, const int64_t* max_iter, const double* dhist,
-                         const int64_t* hoff, int64_t* iters, int32_t* status, double* const* res_hist) {
+                         const int64_t* hoff, int64_t* iters, int32_t* status, double* const* res_hist,
+                         const int64_t* coff = nullptr, double* const* coef = nullptr) {
   bool all = true;
   for (int k = 0; k < ns; ++k) {
     const SolveTail tail(fin[k], max_iter[k]);
@@ -273,6 +282,11 @@ inline int report_states(int ns, const PcgState* fin, const int64_t* max_iter, c
     if (res_hist && res_hist[k]) {
       LSPCG_HIP(hipMemcpy(res_hist[k], dhist + hoff[k], sizeof(double) * tail.written, hipMemcpyDeviceToHost));
       tail.nan_fill(res_hist[k]);
+    }
+    if (coef && coef[k]) {
+      if (tail.pairs() > 0)
+        LSPCG_HIP(hipMemcpy(coef[k], dhist + coff[k], sizeof(double) * 2 * tail.pairs(), hipMemcpyDeviceToHost));
+      tail.nan_fill_coef(coef[k]);
     }
   }
   return all ? LSPCG_OK : LSPCG_NOT_CONVERGED;

@@ -200,21 +200,32 @@ class PreconditionedConjugateGradient:
                 and k[2] == float(epsilon))
 
     def solve(self, b: torch.Tensor, x: torch.Tensor, rtol: float = 1e-6, max_iter: int = 0,
-              return_history: bool = False):
-        """Device-tensor form: returns ``(iters, converged, solve_time_s[, res_hist])``."""
+              return_history: bool = False, return_coefficients: bool = False):
+        """Device-tensor form: returns ``(iters, converged, solve_time_s[, res_hist][, (rho, pi)])``.
+        ``return_coefficients``: the loop's own scalars ρ_k = r_k·z_k and π_k = p_k·q_k of the ``iters``
+        completed iterations (``lspcg_solver_solve_coef``) -- the Lanczos coefficients of M⁻¹A that
+        :mod:`.spectrum` turns into its extreme eigenvalues.  The solve itself is the same, bit for bit."""
         self._check_vector("b", b)
         self._check_vector("x", x)
         mi = int(max_iter) if max_iter and max_iter > 0 else self.n
         it = C.c_int64()
         ms = C.c_double()
         hist = np.empty(mi + 2, dtype=np.float64) if return_history else None
-        rc = _lib.call("lspcg_solver_solve", self.handle, _ptr(b), _ptr(x), float(rtol), mi, C.byref(it),
-                       hist.ctypes.data_as(_lib.p_f64) if hist is not None else None, C.byref(ms),
-                       allow_not_converged=True)
+        hp = hist.ctypes.data_as(_lib.p_f64) if hist is not None else None
+        if return_coefficients:
+            coef = np.empty(2 * (mi + 1), dtype=np.float64)
+            rc = _lib.call("lspcg_solver_solve_coef", self.handle, _ptr(b), _ptr(x), float(rtol), mi, C.byref(it), hp,
+                           C.byref(ms), coef.ctypes.data_as(_lib.p_f64), allow_not_converged=True)
+        else:
+            rc = _lib.call("lspcg_solver_solve", self.handle, _ptr(b), _ptr(x), float(rtol), mi, C.byref(it), hp,
+                           C.byref(ms), allow_not_converged=True)
         self.last_converged = rc == _lib.OK
         out = (it.value, rc == _lib.OK, ms.value / 1e3)
         if return_history:
             out = out + (hist[: min(it.value, mi) + 1].copy(),)  # NaN after a non-finite stop (lspcg.h)
+        if return_coefficients:
+            pairs = coef[: 2 * it.value].reshape(-1, 2)
+            out = out + ((pairs[:, 0].copy(), pairs[:, 1].copy()),)
         return out
 
     def solve_multi(self, B: torch.Tensor, X: torch.Tensor, rtol: float = 1e-6, max_iter: int = 0,
@@ -428,9 +439,12 @@ class BatchedConjugateGradient:
                                  f"on {self.ctx.torch_device}")
         return vs
 
-    def solve(self, bs, xs, rtol: float = 1e-6, max_iter: int = 0, return_history: bool = False):
+    def solve(self, bs, xs, rtol: float = 1e-6, max_iter: int = 0, return_history: bool = False,
+              return_coefficients: bool = False):
         """Solve every system from its x (in place).  Returns ``(results, solve_time_s)`` with
-        ``results[k] = (iters, converged[, res_hist])``; the time is the whole batch's."""
+        ``results[k] = (iters, converged[, res_hist][, (rho, pi)])``; the time is the whole batch's.
+        ``return_coefficients``: every system's own ρ_k, π_k, as the single solver's ``solve`` returns
+        them (``lspcg_batch_solve_coef``)."""
         bs = self._check("b", bs)
         xs = self._check("x", xs)
         k = len(self.n)
@@ -440,13 +454,22 @@ class BatchedConjugateGradient:
         ms = C.c_double()
         hists = [np.empty(m + 2, dtype=np.float64) for m in mi] if return_history else None
         hp = (_lib.p_f64 * k)(*[h.ctypes.data_as(_lib.p_f64) for h in hists]) if hists else None
-        _lib.call("lspcg_batch_solve", self.handle, (C.c_void_p * k)(*[b.data_ptr() for b in bs]),
-                  (C.c_void_p * k)(*[x.data_ptr() for x in xs]), float(rtol), int(max_iter) if max_iter else 0,
-                  it, stt, hp, C.byref(ms), allow_not_converged=True)
+        args = (self.handle, (C.c_void_p * k)(*[b.data_ptr() for b in bs]),
+                (C.c_void_p * k)(*[x.data_ptr() for x in xs]), float(rtol), int(max_iter) if max_iter else 0,
+                it, stt, hp, C.byref(ms))
+        if return_coefficients:
+            coefs = [np.empty(2 * (m + 1), dtype=np.float64) for m in mi]
+            cp = (_lib.p_f64 * k)(*[c.ctypes.data_as(_lib.p_f64) for c in coefs])
+            _lib.call("lspcg_batch_solve_coef", *args, cp, allow_not_converged=True)
+        else:
+            _lib.call("lspcg_batch_solve", *args, allow_not_converged=True)
         res = []
         for j in range(k):
             r = (int(it[j]), stt[j] == _lib.OK)
             if hists:
                 r = r + (hists[j][: min(int(it[j]), mi[j]) + 1].copy(),)
+            if return_coefficients:
+                pairs = coefs[j][: 2 * int(it[j])].reshape(-1, 2)
+                r = r + ((pairs[:, 0].copy(), pairs[:, 1].copy()),)
             res.append(r)
         return res, ms.value / 1e3

@@ -94,12 +94,19 @@ def _converge_iters(ws, sample: GraphSample) -> float:
     return float(pcg(ws.system_matrix(sample), r, L, ws.epsilon, device="cuda")[0])
 
 
+def _converge_cond(ws, sample: GraphSample) -> float:
+    """``Val/cuda_neural_cond``: κ(M⁻¹A) with the current L on the same sample, from a solve of its
+    own with a random start (``ws.condition_number``: the mask is no start for a spectrum estimate)."""
+    return float(ws.condition_number(sample, "neural").cond)
+
+
 def fit(ws, dataset: Sequence[GraphSample], batch_size: int = BATCH_SIZE, max_epochs: int = MAX_EPOCHS,
         split_train: float = SPLIT_TRAIN, check_val_every_n_epoch: int = CHECK_VAL_EVERY_N_EPOCH,
         accumulate_grad_batches: int = ACCUMULATE_GRAD_BATCHES, gradient_clip_val: Optional[float] = GRADIENT_CLIP_VAL,
         optimizer: Optional[dict] = None, scheduler: Optional[dict] = None, seed: int = SEED,
         out_dir: Optional[str] = None, checkpoint_every_n_epochs: int = CHECKPOINT_EVERY_N_EPOCHS,
-        check_converge: bool = False, resume: Optional[str] = None, verbose: bool = False) -> list:
+        check_converge: bool = False, resume: Optional[str] = None, verbose: bool = False,
+        val_cond: bool = False) -> list:
     """Train ``ws.gnn`` on ``dataset`` (samples built with ``is_inference=False``; anything with
     ``len`` and integer indexing; each sample is moved to the device on first use and kept there).
     Defaults are the reference's (the constants above).
@@ -109,7 +116,9 @@ def fit(ws, dataset: Sequence[GraphSample], batch_size: int = BATCH_SIZE, max_ep
     * the schedule is stepped per epoch: epoch ``e`` trains with ``lr(e)``.
     * every ``check_val_every_n_epoch`` epochs ``Val/Loss`` is the mean loss over the validation
       samples at batch size 1; with ``check_converge`` the first one also gives
-      ``Val/cuda_neural_iter`` (PCG with the current L, rhs = mask).
+      ``Val/cuda_neural_iter`` (PCG with the current L, rhs = mask); with ``val_cond`` it also gives
+      ``Val/cuda_neural_cond``, the condition number of the preconditioned system estimated from a
+      separate solve with a random start (``spectrum.condition_number``, rtol 1e-8).
     * one dict per epoch goes to ``ws.history`` (returned) and, with ``out_dir``, to
       ``out_dir/metrics.jsonl``; checkpoints to ``out_dir/checkpoints/epoch=NN.ckpt`` every
       ``checkpoint_every_n_epochs`` epochs and after the last one (``ws.last_checkpoint``).
@@ -171,6 +180,8 @@ def fit(ws, dataset: Sequence[GraphSample], batch_size: int = BATCH_SIZE, max_ep
             row["Val/Loss"] = float(_val_loss(ws, [sample(i) for i in val_idx]))
             if check_converge:
                 row["Val/cuda_neural_iter"] = _converge_iters(ws, sample(val_idx[0]))
+            if val_cond:
+                row["Val/cuda_neural_cond"] = _converge_cond(ws, sample(val_idx[0]))
         ws.history.append(row)
         if out is not None:
             with open(out / "metrics.jsonl", "a") as f:
@@ -219,6 +230,8 @@ def main(argv=None):
                     help="a yaml file in the reference's key layout (batch_size, epsilon, seed, workspace, split.train, "
                          "optimizer, scheduler, trainer.*, checkpoint.every_n_epochs, loss, data); flags override it")
     ap.add_argument("--check-converge", action="store_true")
+    ap.add_argument("--val-cond", action="store_true",
+                    help="log Val/cuda_neural_cond: the condition number of M^-1 A on the first validation sample")
     args = ap.parse_args(argv)
     cfg = _load_config(args.config)
     pick = lambda flag, *keys, default=None: flag if flag is not None else _dig(cfg, keys, default)
@@ -282,7 +295,8 @@ def main(argv=None):
                   gradient_clip_val=float(pick(args.clip, "trainer", "gradient_clip_val", default=GRADIENT_CLIP_VAL)),
                   optimizer=optimizer, scheduler=scheduler, seed=seed, out_dir=args.out,
                   checkpoint_every_n_epochs=int(_dig(cfg, ("checkpoint", "every_n_epochs"), CHECKPOINT_EVERY_N_EPOCHS)),
-                  check_converge=bool(args.check_converge), resume=args.resume, verbose=True)
+                  check_converge=bool(args.check_converge), resume=args.resume, verbose=True,
+                  val_cond=bool(args.val_cond))
     if args.out:
         print(f"last checkpoint: {ws.last_checkpoint}")
     return ws, history

@@ -110,7 +110,12 @@ def load_checkpoint_weights_only(path: str):
     return ck
 
 
+COND_KINDS = ("neural", "none", "diag", "ainv", "ichol")  # the columns of the reference's cond.py:83-89
+
+
 class SimpleInferenceWorkspace:
+    neural_precond = "ext_spai"  # the solver kind of this workspace's own preconditioner
+
     def __init__(self, node_features: int, edge_features: int, block_size: int = 1, epsilon: float = 3e-3,
                  gnn: Optional[dict] = None, seed: Optional[int] = 0, device: Union[str, torch.device] = "cuda",
                  loss_name: str = "RelativeL2Loss_ANorm", loss_params: Optional[dict] = None):
@@ -310,8 +315,34 @@ class SimpleInferenceWorkspace:
         return self._assemble(s, s.matrix_values, block_output)
 
 
+    def condition_number(self, sample: GraphSample, kind: str = "neural", **kw):
+        """κ(M⁻¹A) of ``sample``'s system under preconditioner ``kind`` -- the reference's ``cond.py``
+        columns ``neural, none, diag, ainv, ichol`` -- from one PCG solve's scalars
+        (``spectrum.condition_number``; ``**kw``: its ``start, seed, rtol, max_iter``).  ``neural`` is
+        this workspace's own preconditioner on its inferred L; the baselines are the solvers
+        ``get_cg_iter_time`` builds for ``none / diagonal / ainv / ic``.  AINV(0) and IC(0) factor
+        scalar CSR only, so for them a block-3 sample's A is assembled as the scalar CSR of
+        ``to_csr_cpu`` (what cond.py:110 hands its factorisations), not as BSR."""
+        from . import spectrum
+        from .linalg import PreconditionedConjugateGradient
+
+        if kind not in COND_KINDS:
+            raise ValueError(f"unknown kind {kind!r}; expected one of {COND_KINDS}")
+        s = sample if sample.x.is_cuda else sample.to(self.device)
+        scalar_only = kind in ("ainv", "ichol")
+        A = self.system_matrix(s, block_output=False if scalar_only else None)
+        method = {"neural": self.neural_precond, "none": "none", "diag": "diagonal", "ainv": "ainv", "ichol": "ic"}[kind]
+        solver = PreconditionedConjugateGradient(A, device="cuda", preconditioner=method, dtype=np.float64)
+        if kind == "neural":
+            L, _ = self.inference_step(s)
+            solver.set_spai(L, self.epsilon, block_size=L.block_size)
+        return spectrum.condition_number(solver, **kw)
+
+
 class ScaledInferenceWorkspace(SimpleInferenceWorkspace):
     """scaled_workspace.py:199-212: L <- L · diag(rsqrt(diag(A) + 1e-7)), solved with ext_spai_scaled."""
+
+    neural_precond = "ext_spai_scaled"
 
     def _step_diag(self, batch: GraphSample) -> Optional[torch.Tensor]:
         assert batch.inv_diag is not None, "Relying on batch.inv_diag to maintain stability"
