@@ -116,7 +116,7 @@ int lspcg_spmv(lspcg_ctx* ctx, const lspcg_mat* A, const void* x, void* y);
  * same values and dtype and 16-bit column offsets where they fit, that lspcg_spmv then uses -- the
  * results keep the same bits.  *kind (nullable) = the column storage: 1 (SELL-DIA: a sorted scalar
  * CSR whose 64-row slices have <= 16 distinct row-relative offsets col - row, one value slot per
- * offset and a row mask, no column array), 16 (16-bit offsets from the slice's first row), 17
+ * offset and a lane mask per slot, no column array), 16 (16-bit offsets from the slice's first row), 17
  * (SELL-64J: lanes sorted by row length, each 4-entry group stored for its active lanes only), 18
  * (SELL-64X: SELL-64J reading x from an LDS copy of each 256-row tile's blocks), 32 (int32
  * columns), or 0 when the matrix stays on the CSR / BSR kernel (irregular row lengths).  A numbering

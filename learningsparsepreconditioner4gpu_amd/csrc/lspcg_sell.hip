@@ -76,7 +76,8 @@ __global__ void k_sell_fit16(int64_t n, const int32_t* __restrict__ rowptr, cons
 // takes the wave minimum m of the lanes' current heads, appends it and advances the lanes whose head
 // equals m, so with sorted rows the dictionary comes out ascending and duplicate-free.  cnt[s] =
 // D_s.  flag bit 0: some slice has more than 16 offsets, or some row is not sorted (a lane's next
-// head not above the value it just consumed) -- no SELL-DIA.
+// head not above the value it just consumed) -- no SELL-DIA.  flag[2]: the largest column (sorted
+// rows: the largest last entry), one atomic per slice.
 __global__ void k_sdia_dict(int64_t n, int64_t ns, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                             int32_t* __restrict__ dict, int32_t* __restrict__ cnt, int* __restrict__ flag) {
   const int64_t s = int64_t(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -113,12 +114,16 @@ __global__ void k_sdia_dict(int64_t n, int64_t ns, const int32_t* __restrict__ r
     if (lane == 0) atomicOr(flag, 1);
     return;
   }
+  int top = e > 0 && i < n && rowptr[i] < e ? colind[e - 1] : 0;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) top = max(top, __shfl_xor(top, d, 64));
+  if (lane == 0) atomicMax(flag + 2, top);
   if (lane < kSdiaMax) dict[kSdiaMax * s + lane] = lane < nd ? mine : 0;
   if (lane == 0) cnt[s] = nd;
 }
 
-// row masks: bit j of row i <=> the row has the offset dict[16 s + j]
-__global__ void k_sdia_mask(int64_t n, int64_t ns, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+// BSELL-DIA's row masks (block rows): bit j of row i <=> the row has the offset dict[16 s + j]
+__global__ void k_bsdia_mask(int64_t n, int64_t ns, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                             const int32_t* __restrict__ dict, const int32_t* __restrict__ gp, uint16_t* __restrict__ mask) {
   for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < ns * kSellC; i += int64_t(gridDim.x) * blockDim.x) {
     const int64_t s = i / kSellC;
@@ -137,18 +142,55 @@ __global__ void k_sdia_mask(int64_t n, int64_t ns, const int32_t* __restrict__ r
   }
 }
 
+// lane masks, one wave per slice: bit l of mask[16 s + j] <=> row 64 s + l has the offset
+// dict[16 s + j] (one ballot per slot; the words of the slots past the slice's count are 0)
+__global__ void __launch_bounds__(256) k_sdia_mask(int64_t n, int64_t ns, const int32_t* __restrict__ rowptr,
+                                                   const int32_t* __restrict__ colind, const int32_t* __restrict__ dict,
+                                                   const int32_t* __restrict__ gp, uint64_t* __restrict__ mask) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t s = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); s < ns; s += int64_t(gridDim.x) * 4) {  // wave-uniform
+    const int64_t i = s * kSellC + lane;
+    unsigned m = 0;
+    if (i < n) {
+      const int nd = gp[s + 1] - gp[s];
+      int j = 0;
+      for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+        const int off = int(int64_t(colind[k]) - i);
+        while (j < nd && dict[kSdiaMax * s + j] != off) ++j;  // both ascending
+        m |= 1u << j;
+        ++j;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kSdiaMax; ++j) {
+      const uint64_t word = __ballot((m >> j) & 1u);
+      if (lane == j) mask[kSdiaMax * s + j] = word;
+    }
+  }
+}
+
+// row `lane` of a slice's 16 lane masks: bit j <=> the row has slot j
+__device__ __forceinline__ unsigned sdia_row_mask(const uint64_t* __restrict__ words, int lane) {
+  unsigned m = 0;
+#pragma unroll
+  for (int j = 0; j < kSdiaMax; ++j) m |= unsigned((words[j] >> lane) & 1u) << j;
+  return m;
+}
+
 // values: slot j of row i holds the row's entry number popcount(mask & (2^j - 1)) when bit j is set
+// (256 threads: a thread keeps its lane, so its row mask is gathered once per slice)
 template <typename VS, typename VD>
-__global__ void k_sdia_fill(int64_t n, int64_t ns, const int32_t* __restrict__ gp, const uint16_t* __restrict__ mask,
-                            const int32_t* __restrict__ rowptr, const VS* __restrict__ src, VD* __restrict__ dst) {
+__global__ void __launch_bounds__(256) k_sdia_fill(int64_t n, int64_t ns, const int32_t* __restrict__ gp,
+                                                   const uint64_t* __restrict__ mask, const int32_t* __restrict__ rowptr,
+                                                   const VS* __restrict__ src, VD* __restrict__ dst) {
   for (int64_t s = blockIdx.x; s < ns; s += gridDim.x) {
     const int64_t g0 = gp[s];
     const int32_t slots = kSellC * (gp[s + 1] - gp[s]);
+    const unsigned m = sdia_row_mask(mask + kSdiaMax * s, threadIdx.x & 63);
     for (int32_t p = threadIdx.x; p < slots; p += blockDim.x) {
       const int lane = p & 63;
       const int j = p >> 6;
       const int64_t i = s * kSellC + lane;
-      const unsigned m = mask[i];
       VD v = VD(0);
       if (i < n && ((m >> j) & 1u)) v = VD(src[rowptr[i] + __builtin_popcount(m & ((1u << j) - 1u))]);
       dst[kSellC * g0 + p] = v;
@@ -580,7 +622,8 @@ static int build_head(int64_t nnz, double max_pad, hipStream_t st, SellPattern* 
 // SELL-DIA / BSELL-DIA attempt on P's row graph (k_sdia_dict and k_sdia_mask run on block rows and
 // block columns for bs 3), in two halves so that the caller fetches flag together with whatever else
 // it asked the device, in one host wait.  dia_enqueue: the slices' dictionaries, their sizes' prefix;
-// flag[0] |= 1 when there is no such layout (k_sdia_dict), flag[1] = its slot total.
+// flag[0] |= 1 when there is no such layout (k_sdia_dict), flag[1] = its slot total, flag[2] = the
+// largest column (of the row graph).
 struct DiaScratch {
   int32_t* dict = nullptr;
   int32_t* gp = nullptr;
@@ -595,7 +638,7 @@ static int dia_enqueue(const SellPattern& P, const int32_t* colind, int* flag, D
   return scan_counts(cnt, D->gp, P.ns, B, st, flag + 1, nullptr);
 }
 // dia_try, with the host's copy of flag: *taken = true when the layout exists and stores at most
-// `budget` slots; P then holds it (gp, dict, groups, the row masks in col).  B is the attempt's scratch
+// `budget` slots; P then holds it (gp, dict, groups, the lane masks in col, xn).  B is the attempt's scratch
 // (the caller's flag included): when taken it is freed here, before the mask kernel is enqueued, so
 // that no hipFree waits behind that kernel.
 static int dia_try(const int32_t* colind, const DiaScratch& D, const int* flag_h, int64_t budget, DevBuf& B,
@@ -606,10 +649,16 @@ static int dia_try(const int32_t* colind, const DiaScratch& D, const int* flag_h
   P->dict = B.keep(D.dict);
   P->groups = flag_h[1];
   P->col_bits = 1;
-  LSPCG_HIP(hipMalloc(&P->col, sizeof(uint16_t) * kSellC * std::max<int64_t>(P->ns, 1)));
+  P->xn = int64_t(P->bs) * (int64_t(flag_h[2]) + 1);
+  // 128 B per slice either way: 16 lane masks (SELL-DIA) or 64 row masks (BSELL-DIA)
+  LSPCG_HIP(hipMalloc(&P->col, sizeof(uint64_t) * kSdiaMax * std::max<int64_t>(P->ns, 1)));
   B.release();
-  hipLaunchKernelGGL(k_sdia_mask, dim3(fill_grid(P->ns * kSellC)), dim3(kThreads), 0, st, P->nb, P->ns, P->rowptr, colind,
-                     P->dict, P->gp, static_cast<uint16_t*>(P->col));
+  if (P->bs == 3)
+    hipLaunchKernelGGL(k_bsdia_mask, dim3(fill_grid(P->ns * kSellC)), dim3(kThreads), 0, st, P->nb, P->ns, P->rowptr,
+                       colind, P->dict, P->gp, static_cast<uint16_t*>(P->col));
+  else
+    hipLaunchKernelGGL(k_sdia_mask, dim3(slice_grid((P->ns + 3) / 4)), dim3(256), 0, st, P->nb, P->ns, P->rowptr, colind,
+                       P->dict, P->gp, static_cast<uint64_t*>(P->col));
   LSPCG_HIP(hipGetLastError());
   return LSPCG_OK;
 }
@@ -750,16 +799,16 @@ int sell_build_pattern(int64_t n, int64_t nnz, const int32_t* rowptr, const int3
   if (n) {
     DevBuf B;
     DiaScratch D;
-    int* flag = nullptr;     // [bit 0: no SELL-DIA, bit 1: some offset beyond 16 bits | SELL-DIA slots]
-    int flag_h[2] = {1, 0};
-    if (int rc = B.get(&flag, 2)) return rc;
+    int* flag = nullptr;     // [bit 0: no SELL-DIA, bit 1: some offset beyond 16 bits | SELL-DIA slots | its largest column]
+    int flag_h[3] = {1, 0, 0};
+    if (int rc = B.get(&flag, 3)) return rc;
     LSPCG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flag), (cols & kSellColDia) ? 0 : 1, 1, st));
-    LSPCG_HIP(hipMemsetAsync(flag + 1, 0, sizeof(int), st));
+    LSPCG_HIP(hipMemsetAsync(flag + 1, 0, 2 * sizeof(int), st));
     if (cols & kSellColDia)
       if (int rc = dia_enqueue(P, colind, flag, B, st, &D)) return rc;
     if (cols & kSellCol16)
       hipLaunchKernelGGL(k_sell_fit16, dim3(fill_grid(n)), dim3(kThreads), 0, st, n, rowptr, colind, flag, 2);
-    if (int rc = read_words(flag_h, flag, 2, st)) return rc;
+    if (int rc = read_words(flag_h, flag, 3, st)) return rc;
     fits16 = fits16 && !(flag_h[0] & 2);
     // SELL-DIA when it fits and stores no more slots than the 4-entry groups
     if (int rc = dia_try(colind, D, flag_h, 4 * P.groups, B, st, &P, &taken)) return rc;
@@ -802,11 +851,11 @@ int bsell_build_pattern(int64_t nb, int64_t nnzb, const int32_t* rowptr, const i
     DevBuf B;
     DiaScratch D;
     int* flag = nullptr;
-    int flag_h[2] = {1, 0};  // [no BSELL-DIA, BSELL-DIA slots]
-    if (int rc = B.get(&flag, 2)) return rc;
-    LSPCG_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), st));
+    int flag_h[3] = {1, 0, 0};  // [no BSELL-DIA, BSELL-DIA slots, largest block column]
+    if (int rc = B.get(&flag, 3)) return rc;
+    LSPCG_HIP(hipMemsetAsync(flag, 0, 3 * sizeof(int), st));
     if (int rc = dia_enqueue(P, colind, flag, B, st, &D)) return rc;
-    if (int rc = read_words(flag_h, flag, 2, st)) return rc;
+    if (int rc = read_words(flag_h, flag, 3, st)) return rc;
     // a slice whose distinct offsets outnumber its longest row pads a little more than BSELL-64
     // (C4: 24,574 vs 24,572 slots); the column loads it drops are worth up to 1/16 more slots
     if (int rc = dia_try(colind, D, flag_h, P.groups + P.groups / 16, B, st, &P, &taken)) return rc;
@@ -836,12 +885,25 @@ static void with_value_types(int src_dtype, int dst_dtype, F f) {
   else f(float(), double());
 }
 
+// the zeroed surplus slots behind a new value array (slice-diagonal layouts: kSdiaPadSlots)
+static int zero_surplus(const SellPattern& P, void* v, size_t es, hipStream_t st) {
+  if (P.alloc_slots() > P.slots())
+    LSPCG_HIP(hipMemsetAsync(static_cast<char*>(v) + es * P.slots(), 0, es * (P.alloc_slots() - P.slots()), st));
+  return LSPCG_OK;
+}
+
 int sell_fill_values(const SellPattern& P, const int32_t* colind, const void* src, int src_dtype, int dst_dtype,
                      hipStream_t st, void** out) {
   const size_t es = dst_dtype == LSPCG_F32 ? 4 : 8;
   void* v = *out;  // an existing array of this pattern and dtype is refilled in place
   const bool mine = v == nullptr;
-  if (!v) LSPCG_HIP(hipMalloc(&v, es * std::max<int64_t>(P.slots(), 1)));
+  if (!v) {
+    LSPCG_HIP(hipMalloc(&v, es * std::max<int64_t>(P.alloc_slots(), 1)));
+    if (int rc = zero_surplus(P, v, es, st)) {
+      (void)hipFree(v);
+      return rc;
+    }
+  }
   const dim3 g(slice_grid(P.ns)), b(256);
   if (P.ns)
     with_value_types(src_dtype, dst_dtype, [&](auto vs, auto vd) {
@@ -854,7 +916,7 @@ int sell_fill_values(const SellPattern& P, const int32_t* colind, const void* sr
       if (P.jagged())
         hipLaunchKernelGGL((k_jag_fill<VS, VD>), g, b, 0, st, P.n, P.ns, P.gp, P.jc, P.lmap, P.rowptr, colind, s, no16, d);
       else if (P.col_bits == 1)
-        hipLaunchKernelGGL((k_sdia_fill<VS, VD>), g, b, 0, st, P.n, P.ns, P.gp, static_cast<const uint16_t*>(P.col),
+        hipLaunchKernelGGL((k_sdia_fill<VS, VD>), g, b, 0, st, P.n, P.ns, P.gp, static_cast<const uint64_t*>(P.col),
                            P.rowptr, s, d);
       else
         hipLaunchKernelGGL((k_sell_fill<VS, VD>), g, b, 0, st, P.n, P.ns, P.gp, P.rowptr, colind, s, no32, no16, d);
@@ -873,7 +935,13 @@ int bsell_fill_values(const SellPattern& P, const void* src, int src_dtype, int 
   const size_t es = dst_dtype == LSPCG_F32 ? 4 : 8;
   void* v = *out;  // an existing array of this pattern and dtype is refilled in place
   const bool mine = v == nullptr;
-  if (!v) LSPCG_HIP(hipMalloc(&v, es * std::max<int64_t>(576 * P.groups, 1)));
+  if (!v) {
+    LSPCG_HIP(hipMalloc(&v, es * std::max<int64_t>(P.alloc_slots(), 1)));
+    if (int rc = zero_surplus(P, v, es, st)) {
+      (void)hipFree(v);
+      return rc;
+    }
+  }
   const dim3 g(slice_grid(P.ns)), b(256);
   if (P.ns)
     with_value_types(src_dtype, dst_dtype, [&](auto vs, auto vd) {

@@ -44,12 +44,29 @@ constexpr int16_t kSellPad16 = -32768;
 // 5, boundary rows use subsets).  Each slice s keeps its D_s <= 16 distinct offsets, ascending, in
 // dict[16 s + j] and stores its rows' values slot-major, ONE slot per dictionary entry:
 //     vals[64 (gp[s] + j) + lane]   (row 64 s + lane, column row + dict[16 s + j]),
-// with bit j of mask[64 s + lane] set where the row has that entry (absent entries: value 0, bit
-// clear, never added).  Rows are sorted, so slot order = the row's column order = scipy's sum
-// order.  No column storage at all: the offset of slot j is wave-uniform (a scalar register), the
-// x / r / t / p "gather" of slot j is one contiguous 64-entry load, and a row costs D_s values +
-// 2 bytes of mask (Kuhn: 15 slots per row where SELL-64's 4-entry groups store 16).
+// with bit lane of the LANE MASK mask[16 s + j] (64-bit words) set where the row has that entry
+// (absent entries: value 0, bit clear, never added; the words of slots j >= D_s are 0).  Rows are
+// sorted, so slot order = the row's column order = scipy's sum order.  No column storage at all: the
+// offset of slot j is wave-uniform (a scalar register), the x / r / t / p "gather" of slot j is one
+// contiguous 64-entry load, and a row costs D_s values + 2 bytes of mask (128 B per slice; Kuhn: 15
+// slots per row where SELL-64's 4-entry groups store 16).
+// Addressing: everything per slot is scalar.  A slot's mask word comes through a
+// scalar load and is the select's lane mask as it stands.  The values of slot j are read at the
+// slice's per-lane base + the compile-time offset 64 j, with no clamp: a surplus slot of the last
+// batch reads the next slice's values (masked), and every value array ends in kSdiaPadSlots zeroed
+// slots so that the last slice's surplus stays inside the allocation (BSELL-DIA keeps 16-bit row masks,
+// the clamped slot index and the per-lane select: BsdiaSlice).  The vector window of slot j
+// is loaded unconditionally at base + dict[j] + lane through a range-checked buffer load whose
+// resource covers exactly the xn vector entries the pattern reads: a window that starts before row
+// 0 or ends past xn returns 0 for those lanes, which the mask never adds (sdia_ranged: plain
+// vectors of <= kSdiaRangedMax entries; fused gathers and longer vectors keep the per-lane select
+// that reads the slice's first row in masked lanes).
 constexpr int kSdiaMax = 16;       // slots (distinct offsets) per slice
+constexpr int kSdiaPadSlots = kSdiaMax - 1;  // zeroed slots behind a SELL-DIA value array
+// Largest vector (entries) read through the range-checked loads: the 32-bit byte offset
+// 8 (base + dict[j] + lane) of a column in (-n, n + xn + 64) must neither wrap into [0, 8 xn) from
+// below (2^32 - 8 n >= 8 xn) nor from above (8 (n + xn + 64) <= 2^32); 2^27 entries keep both.
+constexpr int64_t kSdiaRangedMax = int64_t(1) << 27;
 // column-storage choices for sell_build_pattern (bit mask); int32 columns are always possible
 constexpr int kSellCol16 = 1;
 constexpr int kSellColDia = 2;
@@ -122,7 +139,8 @@ struct SellPattern {
   int64_t groups = 0;              // gp[ns]: 4-entry groups (bs 1) / block slots (bs 3) / DIA slots per lane, summed
   int32_t* gp = nullptr;           // [ns+1] exclusive prefix of per-slice groups (slots) per row
   void* col = nullptr;             // [256*groups] (bs 1) / [64*groups] (bs 3) int32 columns or int16 offsets;
-                                   // SELL-DIA (col_bits 1): [64*ns] uint16 row masks
+                                   // SELL-DIA (col_bits 1): [16*ns] 64-bit lane masks, one per slot
+                                   // (BSELL-DIA: [64*ns] uint16 row masks)
   int col_bits = kSellInt32;
   int32_t* dict = nullptr;         // SELL-DIA: [16*ns] ascending row-relative offsets per slice;
                                    // SELL-64C (col_bits 8): [64*ns], col = [256*groups] uint8 codes
@@ -134,7 +152,8 @@ struct SellPattern {
   int32_t* xlp = nullptr;          // SELL-64X: [ntiles+1] block-list prefix per 256-row tile
   int32_t* xl = nullptr;           // SELL-64X: the tiles' ascending x-block lists
   int kx = 0;                      // SELL-64X: the longest list
-  int64_t xn = 0;                  // SELL-64X: vector entries read (largest column + 1; > n for dist_pcg's halo)
+  int64_t xn = 0;                  // SELL-64X, SELL-DIA, BSELL-DIA: vector entries read (largest column + 1;
+                                   // > n for dist_pcg's halo)
   const int32_t* rowptr = nullptr; // CSR row pointer (row lengths), not owned
   // Every field above, pointers and values alike, to f: what a launch captured in a graph holds of
   // the pattern (the solver's graph_key).  A new field belongs in the list above AND here.
@@ -145,10 +164,15 @@ struct SellPattern {
   }
   // the jagged element layout (SELL-64J / SELL-64X): gp is an element prefix
   bool jagged() const { return col_bits == kSellJag || col_bits == kSellJagX; }
-  // entries of a value array of this pattern (sell_fill_values allocates this many)
+  // entries of a value array of this pattern
   int64_t slots() const {
     if (bs == 3) return int64_t(576) * groups;  // BSELL-64 / BSELL-DIA: 9 values per block slot
     return jagged() ? elems : (col_bits == kSellDia ? int64_t(64) : int64_t(256)) * groups;
+  }
+  // entries sell_fill_values / bsell_fill_values allocate: slots() + SELL-DIA's zeroed surplus slots
+  // (see kSdiaPadSlots)
+  int64_t alloc_slots() const {
+    return slots() + (col_bits == kSellDia && bs == 1 ? int64_t(kSdiaPadSlots) * 64 : 0);
   }
   void release() {  // the owned arrays (not rowptr)
     auto drop = [](auto*& p) {
@@ -181,9 +205,10 @@ struct SdiaArgs {
   int64_t n;
   int64_t ns;
   const int32_t* gp;
-  const uint16_t* mask;
+  const uint64_t* mask;  // [16 ns] lane masks (BSELL-DIA: the same bytes as [64 ns] uint16 row masks)
   const int32_t* dict;
   const VT* vals;
+  int64_t xn;            // vector entries the pattern reads
 };
 
 // the kernel arguments of a pattern and one of its value arrays (a layout's kernel reads its own fields)
@@ -194,7 +219,7 @@ inline SellArgs<VT, CT> sell_args(const SellPattern& P, const void* vals) {
 }
 template <typename VT>
 inline SdiaArgs<VT> sdia_args(const SellPattern& P, const void* vals) {
-  return {P.n, P.ns, P.gp, static_cast<const uint16_t*>(P.col), P.dict, static_cast<const VT*>(vals)};
+  return {P.n, P.ns, P.gp, static_cast<const uint64_t*>(P.col), P.dict, static_cast<const VT*>(vals), P.xn};
 }
 
 // ---- the SpMV ----------------------------------------------------------------
@@ -649,35 +674,103 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_bsell3(SellArgs<VT, CT> a, Pr
   finish_epi_dots<Epi>(d, epi);
 }
 
-// A SELL-DIA / BSELL-DIA slice's metadata: its slot range (gp), its whole 16-entry offset dictionary
-// (one scalar block load: entries past the slice's count are never used, masked lanes read x[base])
-// and the lane's row mask, loaded in one batch.
+// A SELL-DIA slice's metadata: its slot range (gp) and its whole 16-entry offset
+// dictionary, wave-uniform and loaded in one batch of scalar loads (dictionary entries past the
+// slice's count are 0 and their lane masks are 0: such a slot loads legally and is never added).
+// The lane masks are loaded batch by batch (masks): a ranged kernel needs them only at the adds, so
+// their scalar loads fly beside the batch's value and window loads.
 struct SdiaSlice {
   int32_t g0 = 0, g1 = 0;
-  unsigned msk = 0;
   int32_t dct[kSdiaMax];
+  const uint64_t* mp = nullptr;
   template <typename VT>
-  __device__ __forceinline__ void load(const SdiaArgs<VT>& a, int64_t sl, int lane) {
+  __device__ __forceinline__ void load(const SdiaArgs<VT>& a, int64_t sl) {
     g0 = a.gp[sl];
     g1 = a.gp[sl + 1];
-    msk = gld(a.mask + kSellC * sl + lane);
     const int32_t* dp = a.dict + kSdiaMax * sl;
 #pragma unroll
     for (int j = 0; j < kSdiaMax; ++j) dct[j] = dp[j];
+    mp = a.mask + kSdiaMax * sl;
   }
-  // slot j of a batch: whether this lane's row has it (nd = the slice's slot count), and where its
-  // values start (clamped: the surplus slots of the last batch load the last slot and are masked)
-  __device__ __forceinline__ bool has(int j, int nd) const { return (j < nd) && ((msk >> j) & 1u); }
-  __device__ __forceinline__ int64_t slot(int j, int nd) const { return int64_t(g0 + min(j, nd - 1)); }
+  template <int SB>
+  __device__ __forceinline__ void masks(int j0, uint64_t (&mk)[SB]) const {
+#pragma unroll
+    for (int u = 0; u < SB; ++u) mk[u] = mp[j0 + u];
+  }
+  // this lane's values of slot 0 (slot j: + 64 j entries, a compile-time offset; SELL-DIA)
+  template <typename VT>
+  __device__ __forceinline__ const VT* values(const SdiaArgs<VT>& a, int lane) const {
+    return a.vals + kSellC * int64_t(g0) + lane;
+  }
 };
+// whether this lane's row has the slot of lane mask `word`: the word as the select's condition
+__device__ __forceinline__ bool sdia_has(uint64_t word) { return __builtin_amdgcn_inverse_ballot_w64(word); }
+// acc + v x where the row has the slot, acc untouched (not acc + 0 x) where not.  A select, not a
+// branch: a branch lets the compiler sink the slot's loads behind the mask test, out of the batch.
+template <typename T, typename VT>
+__device__ __forceinline__ T sdia_add(uint64_t word, T acc, VT v, T x) {
+  const T t = acc + T(v) * x;
+  return sdia_has(word) ? t : acc;
+}
 
-// SELL-DIA SpMV (layout: see kSdiaMax): one wave = one 64-row slice of a 256-row tile, SB slots
-// per batch, every load of a batch issued before the first add (value loads and vector loads are
-// independent: the slot's offset is a scalar).  The first tile's metadata is loaded before the
-// prologue's state read: one memory latency before the value / vector loads instead of three in a
-// row (state, gp, dictionary).
-template <typename T, typename VT, int SB, int TH, int MINW, class Pro, class Gx, class Epi>
+// The vector windows of a SELL-DIA slice through range-checked buffer loads (see
+// kSdiaMax): the resource covers the `entries` entries of x, the whole byte offset
+// sizeof(T) * (first + per_lane * lane) is the per-lane offset the hardware checks (first: the
+// window's wave-uniform first entry, possibly negative or past the end), and a lane outside the
+// vector reads 0.  per_lane: entries per row (1; K for K interleaved vectors).
+template <typename T>
+struct SdiaWindow {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "fp32 or fp64 vectors");
+  using u2 = unsigned __attribute__((ext_vector_type(2)));
+  using u4 = unsigned __attribute__((ext_vector_type(4)));
+  __amdgpu_buffer_rsrc_t rs;
+  unsigned lane_b;
+  __device__ __forceinline__ SdiaWindow(const T* x, int64_t entries, int lane, int per_lane)
+      : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x), 0, int(unsigned(entries) * unsigned(sizeof(T))),
+                                             0x00020000)),
+        lane_b(unsigned(lane * per_lane) * unsigned(sizeof(T))) {}
+  // (readfirstlane: `first` is wave-uniform; it keeps the scalar part in scalar registers, so the
+  // per-lane offset is ONE vector add -- otherwise the compiler re-associates the sum into two)
+  __device__ __forceinline__ unsigned offset(int32_t first) const {
+    return unsigned(__builtin_amdgcn_readfirstlane(int(unsigned(first) * unsigned(sizeof(T))))) + lane_b;
+  }
+  __device__ __forceinline__ T at(int32_t first) const {  // the lane's entry of the window at `first`
+    const int off = int(offset(first));
+    if constexpr (sizeof(T) == 8) return __builtin_bit_cast(T, u2(__builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0)));
+    else return __builtin_bit_cast(T, unsigned(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0)));
+  }
+  template <int K>
+  __device__ __forceinline__ void row(int32_t first, T (&v)[K]) const {  // its K entries, in RowK's parts
+    constexpr int W = RowK<T, K>::W;
+    using V = typename RowK<T, K>::V;
+    static_assert(W * sizeof(T) == 8 || W * sizeof(T) == 16, "8- or 16-byte parts");
+#pragma unroll
+    for (int c = 0; c < K / W; ++c) {
+      const int off = int(offset(first) + unsigned(c * W * sizeof(T)));
+      V p;
+      if constexpr (W * sizeof(T) == 16) p = __builtin_bit_cast(V, u4(__builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0)));
+      else p = __builtin_bit_cast(V, u2(__builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0)));
+#pragma unroll
+      for (int w = 0; w < W; ++w) v[c * W + w] = p[w];
+    }
+  }
+};
+// whether a launch on a plain vector (K interleaved ones) may take them: short enough for the
+// 32-bit offset check (kSdiaRangedMax)
+inline bool sdia_ranged(const SellPattern& P, int K = 1) {
+  return P.xn > 0 && int64_t(K) * std::max(P.n, P.xn) <= kSdiaRangedMax;
+}
+
+// SELL-DIA SpMV (layout and addressing: see kSdiaMax): one wave = one 64-row slice of a 256-row
+// tile, SB slots per batch, every load of a batch issued before the first add (value loads and
+// vector loads are independent: the slot's offset is a scalar).  The first tile's metadata is
+// loaded before the prologue's state read: one memory latency before the value / vector loads
+// instead of three in a row (state, gp, dictionary).
+// RANGED (sdia_ranged; Gx = GatherVec): the vector windows are range-checked buffer loads with no
+// per-lane select; otherwise masked lanes gather the slice's first row through gx.
+template <typename T, typename VT, int SB, int TH, int MINW, bool RANGED, class Pro, class Gx, class Epi>
 __global__ void __launch_bounds__(TH, MINW) k_spmv_sdia(SdiaArgs<VT> a, Pro pro, Gx gx, Epi epi) {
+  static_assert(!RANGED || std::is_same<Gx, GatherVec<T>>::value, "range-checked windows read a plain vector");
   constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
@@ -685,11 +778,15 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sdia(SdiaArgs<VT> a, Pro pro,
   SdiaSlice sl;
   {
     const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
-    if (int64_t(blockIdx.x) < ntiles && s < a.ns) sl.load(a, s, lane);
+    if (int64_t(blockIdx.x) < ntiles && s < a.ns) sl.load(a, s);
   }
   if (pro.exit()) return;
   gx.prepare();
   epi.prepare();
+  [[maybe_unused]] const auto win = [&] {
+    if constexpr (RANGED) return SdiaWindow<T>(gx.x, a.xn, lane, 1);
+    else return 0;
+  }();
   DD d[ND];
 #pragma unroll
   for (int j = 0; j < ND; ++j) d[j] = dd_zero();
@@ -697,10 +794,10 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sdia(SdiaArgs<VT> a, Pro pro,
     const int64_t s = tile * (TH / 64) + w;
     const int64_t i = tile * TH + threadIdx.x;
     if (s < a.ns) {  // wave-uniform
-      if (tile != int64_t(blockIdx.x)) sl.load(a, s, lane);
+      if (tile != int64_t(blockIdx.x)) sl.load(a, s);
       const int nd = sl.g1 - sl.g0;
       const int32_t base = int32_t(s * kSellC);
-      const int32_t row = base + lane;
+      const VT* vp = sl.values(a, lane);
       T acc = T(0);
       RowOut<T, 1, Epi> out;
       out.prefetch(epi, i, i < a.n);
@@ -709,18 +806,17 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sdia(SdiaArgs<VT> a, Pro pro,
         if (j0 >= nd) break;  // wave-uniform
         VT v[SB];
         T xv[SB];
-        bool m[SB];
+        uint64_t mk[SB];
+        sl.masks(j0, mk);
 #pragma unroll
         for (int u = 0; u < SB; ++u) {
           const int j = j0 + u;
-          m[u] = sl.has(j, nd);
-          const int32_t c = m[u] ? row + sl.dct[j] : base;
-          v[u] = gld(a.vals + kSellC * sl.slot(j, nd) + lane);
-          xv[u] = gx(c);
+          v[u] = gld(vp + kSellC * j);
+          if constexpr (RANGED) xv[u] = win.at(base + sl.dct[j]);
+          else xv[u] = gx(sdia_has(mk[u]) ? base + lane + sl.dct[j] : base);
         }
 #pragma unroll
-        for (int u = 0; u < SB; ++u)
-          if (m[u]) acc = acc + T(v[u]) * xv[u];
+        for (int u = 0; u < SB; ++u) acc = sdia_add(mk[u], acc, v[u], xv[u]);
       }
       out.emit(epi, i, i < a.n, acc, d);
     }
@@ -733,7 +829,8 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_sdia(SdiaArgs<VT> a, Pro pro,
 // minimum-workgroups bound: as a K parameter of k_spmv_sdia (the vector inside the gather functor,
 // after the prologue's argument) the same loop measured 0.6-2.4 % slower per solve on systems of
 // 65 k - 70 k rows (profiles/sell_kernels_refactor_ab.json, "k_merged_into_k_spmv_sdia").
-template <typename T, typename VT, int K, int SB, int TH, class Pro, class Epi>
+// RANGED (sdia_ranged(P, K)): the windows of K a.xn entries through range-checked loads.
+template <typename T, typename VT, int K, int SB, int TH, bool RANGED, class Pro, class Epi>
 __global__ void __launch_bounds__(TH) k_spmm_sdia(SdiaArgs<VT> a, const T* __restrict__ x, Pro pro, Epi epi) {
   constexpr int ND = Epi::NDOT > 0 ? Epi::NDOT : 1;
   const int lane = threadIdx.x & 63;
@@ -742,9 +839,13 @@ __global__ void __launch_bounds__(TH) k_spmm_sdia(SdiaArgs<VT> a, const T* __res
   SdiaSlice sl;
   {
     const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
-    if (int64_t(blockIdx.x) < ntiles && s < a.ns) sl.load(a, s, lane);
+    if (int64_t(blockIdx.x) < ntiles && s < a.ns) sl.load(a, s);
   }
   if (pro.exit()) return;
+  [[maybe_unused]] const auto win = [&] {
+    if constexpr (RANGED) return SdiaWindow<T>(x, a.xn * K, lane, K);
+    else return 0;
+  }();
   DD d[ND];
 #pragma unroll
   for (int j = 0; j < ND; ++j) d[j] = dd_zero();
@@ -752,10 +853,10 @@ __global__ void __launch_bounds__(TH) k_spmm_sdia(SdiaArgs<VT> a, const T* __res
     const int64_t s = tile * (TH / 64) + w;
     const int64_t i = tile * TH + threadIdx.x;
     if (s < a.ns) {  // wave-uniform
-      if (tile != int64_t(blockIdx.x)) sl.load(a, s, lane);
+      if (tile != int64_t(blockIdx.x)) sl.load(a, s);
       const int nd = sl.g1 - sl.g0;
       const int32_t base = int32_t(s * kSellC);
-      const int32_t row = base + lane;
+      const VT* vp = sl.values(a, lane);
       T acc[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) acc[k] = T(0);
@@ -764,21 +865,19 @@ __global__ void __launch_bounds__(TH) k_spmm_sdia(SdiaArgs<VT> a, const T* __res
         if (j0 >= nd) break;  // wave-uniform
         VT v[SB];
         T xv[SB][K];
-        bool m[SB];
+        uint64_t mk[SB];
+        sl.masks(j0, mk);
 #pragma unroll
         for (int u = 0; u < SB; ++u) {
           const int j = j0 + u;
-          m[u] = sl.has(j, nd);
-          const int32_t c = m[u] ? row + sl.dct[j] : base;
-          v[u] = gld(a.vals + kSellC * sl.slot(j, nd) + lane);
-          RowK<T, K>::load(x + int64_t(c) * K, xv[u]);
+          v[u] = gld(vp + kSellC * j);
+          if constexpr (RANGED) win.row((base + sl.dct[j]) * K, xv[u]);
+          else RowK<T, K>::load(x + int64_t(sdia_has(mk[u]) ? base + lane + sl.dct[j] : base) * K, xv[u]);
         }
 #pragma unroll
         for (int u = 0; u < SB; ++u)
-          if (m[u]) {
 #pragma unroll
-            for (int k = 0; k < K; ++k) acc[k] = acc[k] + T(v[u]) * xv[u][k];
-          }
+          for (int k = 0; k < K; ++k) acc[k] = sdia_add(mk[u], acc[k], v[u], xv[u][k]);
       }
       if (i < a.n) epi.row(i, acc, d);
     }
@@ -786,9 +885,33 @@ __global__ void __launch_bounds__(TH) k_spmm_sdia(SdiaArgs<VT> a, const T* __res
   finish_epi_dots<Epi>(d, epi);
 }
 
+// A BSELL-DIA slice's metadata (BSELL-DIA keeps SELL-DIA's first form: 16-bit ROW masks, a per-lane
+// select for masked lanes and a clamped slot index; the lean form measured 0.6-1.6 us per C4 iteration
+// slower): its slot range (gp), its whole 16-entry offset dictionary
+// (one scalar block load: entries past the slice's count are never used, masked lanes read x[base])
+// and the lane's row mask, loaded in one batch.
+struct BsdiaSlice {
+  int32_t g0 = 0, g1 = 0;
+  unsigned msk = 0;
+  int32_t dct[kSdiaMax];
+  template <typename VT>
+  __device__ __forceinline__ void load(const SdiaArgs<VT>& a, int64_t sl, int lane) {
+    g0 = a.gp[sl];
+    g1 = a.gp[sl + 1];
+    msk = gld(reinterpret_cast<const uint16_t*>(a.mask) + kSellC * sl + lane);
+    const int32_t* dp = a.dict + kSdiaMax * sl;
+#pragma unroll
+    for (int j = 0; j < kSdiaMax; ++j) dct[j] = dp[j];
+  }
+  // slot j of a batch: whether this lane's row has it (nd = the slice's slot count), and where its
+  // values start (clamped: the surplus slots of the last batch load the last slot and are masked)
+  __device__ __forceinline__ bool has(int j, int nd) const { return (j < nd) && ((msk >> j) & 1u); }
+  __device__ __forceinline__ int64_t slot(int j, int nd) const { return int64_t(g0 + min(j, nd - 1)); }
+};
+
 // BSR 3x3 over the BSELL-DIA layout (SELL-DIA's slot dictionary on the block graph + BSELL-64's
 // 9-value lane chunks): k_spmv_sdia's walk with one lane = one block row = 3 scalar rows; slot j of
-// the slice holds the block at block column I + dict[j] (mask bit j), so the x entries of a slot
+// the slice holds the block at block column I + dict[j] (bit j of the block row's mask), so the x entries of a slot
 // are three contiguous 64-block loads at a wave-uniform offset and no column is loaded at all.  The
 // slot order is the row's block column order, c = 0, 1, 2 inside a block: the expanded scalar CSR's
 // summation order.
@@ -799,7 +922,7 @@ __global__ void __launch_bounds__(TH, MINW) k_spmv_bsdia3(SdiaArgs<VT> a, Pro pr
   const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
   const int64_t nb = a.n / 3;
   const int64_t ntiles = (nb + TH - 1) / TH;
-  SdiaSlice sl;
+  BsdiaSlice sl;
   {
     const int64_t s = int64_t(blockIdx.x) * (TH / 64) + w;
     if (int64_t(blockIdx.x) < ntiles && s < a.ns) sl.load(a, s, lane);
@@ -943,16 +1066,20 @@ inline int launch_sell(const SellPattern& P, const void* vals, Gx gx, Pro pro, E
   const dim3 g{unsigned(grid)}, b{kSellWG};
   if (P.col_bits == kSellDia) {
     const SdiaArgs<VT> a = sdia_args<VT>(P, vals);
-    if constexpr (K == 1) {
-      if (P.bs == 3) {
+    // range-checked vector windows wherever the vector is a plain one and short enough (sdia_ranged)
+    by_flag(plain && sdia_ranged(P, K), [&](auto ranged) {
+      constexpr bool RANGED = plain && decltype(ranged)::value;
+      if constexpr (K > 1) {
+        LSPCG_LAUNCH_SPMV((k_spmm_sdia<T, VT, K, spmm_sb<K>(), kSellWG, RANGED, Pro, Epi>), g, b, 0, st, a, gx.x, pro,
+                          epi);
+      } else if (P.bs == 3) {
         LSPCG_LAUNCH_SPMV((k_spmv_bsdia3<T, VT, bsdia_sb<VT>(), kSellWG, MINW, Pro, Gx, Epi>), g, b, 0, st, a, pro, gx,
                           epi);
-        return LSPCG_OK;
+      } else {
+        LSPCG_LAUNCH_SPMV((k_spmv_sdia<T, VT, kSdiaSB, kSellWG, MINW, RANGED, Pro, Gx, Epi>), g, b, 0, st, a, pro, gx,
+                          epi);
       }
-      LSPCG_LAUNCH_SPMV((k_spmv_sdia<T, VT, kSdiaSB, kSellWG, MINW, Pro, Gx, Epi>), g, b, 0, st, a, pro, gx, epi);
-    } else {
-      LSPCG_LAUNCH_SPMV((k_spmm_sdia<T, VT, K, spmm_sb<K>(), kSellWG, Pro, Epi>), g, b, 0, st, a, gx.x, pro, epi);
-    }
+    });
     return LSPCG_OK;
   }
   if constexpr (K == 1) {
