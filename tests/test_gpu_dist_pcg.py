@@ -27,6 +27,8 @@ def _system(kind):
         return A, _cases.spai_like(A), A @ np.ones(6)
     if kind == "kuhn":
         A, mask = P.kuhn_dirichlet(17)
+    elif kind == "delaunay":  # unstructured rows (SELL-64J): the real exchange on an irregular halo
+        A, mask, _ = P.delaunay_heat(5000)
     else:
         A, mask, _ = P.poisson2d_grid(90, 70)
     A = sp.csr_matrix(A)
@@ -35,7 +37,10 @@ def _system(kind):
     return A, _cases.spai_like(A), b
 
 
-def _oracle(A, L, b, rtol):
+def _oracle(A, L, b, rtol, dtype=np.float64):
+    if dtype == np.float32:  # the fp32 scipy cg with correctly rounded dots, as test_world1_fp32
+        ps = O.spai_operator(L.astype(np.float32), EPS)
+        return O.pcg(A.astype(np.float32), b.astype(np.float32), ps, rtol=rtol, dot="exact", dtype=np.float32)
     ps = O.spai_operator(L, EPS) if L is not None else None
     return O.pcg(A, b, ps, rtol=rtol, dot="exact")
 
@@ -91,7 +96,7 @@ def _free_port():
     return p
 
 
-def _rank(rank, world, port, kind, q, blocks=False, overlap=True):  # noqa: C901
+def _rank(rank, world, port, kind, q, blocks=False, overlap=True, dtype=np.float64, rtol=1e-8):  # noqa: C901
     import torch.distributed as dist
 
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), LSPCG_DIST_OVERLAP="1" if overlap else "0")
@@ -105,11 +110,11 @@ def _rank(rank, world, port, kind, q, blocks=False, overlap=True):  # noqa: C901
         r0, r1 = bounds[rank], bounds[rank + 1]
         LT = sp.csr_matrix(L).T.tocsr()
         d = DistributedPCG.from_row_blocks(sp.csr_matrix(A)[r0:r1], sp.csr_matrix(L)[r0:r1], LT[r0:r1], n=A.shape[0],
-                                           bounds=bounds, epsilon=EPS)
+                                           bounds=bounds, epsilon=EPS, dtype=dtype)
     else:
-        d = DistributedPCG(A, L, EPS)
-    it, conv, x, hist = d.solve(b, rtol=1e-8, return_history=True)
-    it_h, conv_h, x_h, hist_h = d.solve_host(b, rtol=1e-8, return_history=True)
+        d = DistributedPCG(A, L, EPS, dtype=dtype)
+    it, conv, x, hist = d.solve(b, rtol=rtol, return_history=True)
+    it_h, conv_h, x_h, hist_h = d.solve_host(b, rtol=rtol, return_history=True)
     same = (it_h, conv_h) == (it, conv) and np.array_equal(hist_h, hist) and torch.equal(x_h, x)
     xg = d.gather_solution(x)
     q.put((rank, it, bool(conv), xg, hist, d.plan.n_own, len(d.plan.halo), same, d.split, d.plan.n_int))
@@ -117,16 +122,26 @@ def _rank(rank, world, port, kind, q, blocks=False, overlap=True):  # noqa: C901
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,blocks,overlap", [(2, False, True), (3, False, True), (3, True, True), (2, False, False)])
-def test_multi_rank_matches_oracle(gpu_ctx, world, blocks, overlap):
+@pytest.mark.parametrize("world,blocks,overlap,kind,dtype", [
+    pytest.param(2, False, True, "kuhn", np.float64, id="2-False-True"),
+    pytest.param(3, False, True, "kuhn", np.float64, id="3-False-True"),
+    pytest.param(3, True, True, "kuhn", np.float64, id="3-True-True"),
+    pytest.param(2, False, False, "kuhn", np.float64, id="2-False-False"),
+    pytest.param(2, False, True, "delaunay", np.float64, id="2-False-True-delaunay-f64"),
+    pytest.param(2, False, True, "delaunay", np.float32, id="2-False-True-delaunay-f32")])
+def test_multi_rank_matches_oracle(gpu_ctx, world, blocks, overlap, kind, dtype):
     """blocks: DistributedPCG.from_row_blocks -- no rank holds the global system.  overlap: own rows
     numbered interior first, the interior rows' SpMVs enqueued while the halo exchange runs
-    (LSPCG_DIST_OVERLAP=0: one row range)."""
-    kind = "kuhn"
+    (LSPCG_DIST_OVERLAP=0: one row range).  delaunay: an unstructured mesh (problems.delaunay_heat(5000)),
+    fp64 and fp32 -- fp32 against the oracle's fp32 scipy cg at rtol 1e-5, counts equal and x within
+    1e-5, as test_world1_fp32."""
+    f32 = dtype == np.float32
+    rtol = 1e-5 if f32 else 1e-8
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_rank, args=(r, world, port, kind, q, blocks, overlap)) for r in range(world)]
+    procs = [ctx.Process(target=_rank, args=(r, world, port, kind, q, blocks, overlap, dtype, rtol))
+             for r in range(world)]
     for p in procs:
         p.start()
     outs = sorted([q.get(timeout=100) for _ in range(world)], key=lambda o: o[0])
@@ -134,12 +149,15 @@ def test_multi_rank_matches_oracle(gpu_ctx, world, blocks, overlap):
         p.join(timeout=60)
         assert p.exitcode == 0
     A, L, b = _system(kind)
-    it_o, x_o, h_o = _oracle(A, L, b, 1e-8)
+    it_o, x_o, h_o = _oracle(A, L, b, rtol, dtype)
     assert sum(o[5] for o in outs) == A.shape[0] and all(o[6] > 0 for o in outs)
     for rank, it, conv, xg, hist, _, _, same, split, _ in outs:
         assert split == overlap, rank
         assert same, rank  # device-side scalars = the host recurrence, bit for bit
         assert conv and it == it_o, (rank, it, it_o)
+        if f32:
+            assert np.linalg.norm(xg - x_o) <= 1e-5 * np.linalg.norm(x_o)
+            continue
         np.testing.assert_allclose(hist, h_o[: it + 1], rtol=1e-12, atol=0)
         assert np.linalg.norm(xg - x_o) <= 1e-12 * np.linalg.norm(x_o)
     assert all(np.array_equal(outs[0][3], o[3]) for o in outs)  # every rank holds the same solution
