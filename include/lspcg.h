@@ -90,6 +90,16 @@ int lspcg_mat_destroy(lspcg_mat* A);
 int lspcg_mat_info(const lspcg_mat* A, int64_t* n, int64_t* nnzb, int* bs, int* dtype);
 /* copy the handle's arrays out (host or device destinations; NULL skips an array) */
 int lspcg_mat_copy_out(const lspcg_mat* A, int32_t* indptr, int32_t* indices, void* vals);
+/* New values for an existing matrix of the same pattern (a time step or a sample on a fixed mesh:
+ * the reference's is_fixed_topology datasets): vals (host or device, of `dtype` = A's dtype)
+ * overwrites A's nnzb*bs*bs values in A's stored order.  indptr / indices (host or device, either
+ * may be NULL = not checked) are compared with A's on the device first; a difference returns
+ * LSPCG_ERR_FORMAT and nothing is written.  A dtype other than A's is LSPCG_ERR_ARG.  The copy a
+ * lspcg_mat_prepare_spmv attached is refilled in place -- same kind, same permutation when it was
+ * analysed on P A P^T -- and lspcg_spmv keeps scipy's bits on the new values.  No solve may be
+ * running on A; a solver created on A must see lspcg_solver_update_matrix before its next solve. */
+int lspcg_mat_set_values(lspcg_mat* A, const int32_t* indptr, const int32_t* indices, const void* vals,
+                         int dtype);
 /* explicit transpose (sorted), replaces csr_matrix(spai.T) of validate.py:176 */
 int lspcg_mat_transpose(const lspcg_mat* A, lspcg_mat** out);
 /* d[i] = A[i,i] (0 where absent), device pointer of the matrix dtype, length n */
@@ -180,6 +190,24 @@ int lspcg_solver_set_ic(lspcg_solver* s, double* t_prec_ms);
  * reference's IncompleteCholeskyPreconditioner(L) of get_pcg_iter_time_scipy_ichol
  * (validate.py:344-419, which takes an external L).  L is copied. */
 int lspcg_solver_set_ic_factor(lspcg_solver* s, const lspcg_mat* L, double* t_prec_ms);
+/* The values of the solver's A handle changed in place (lspcg_mat_set_values, lspcg_assemble_into),
+ * the pattern did not.  Drains the solver's stream and redoes what depends on values: P A P^T through
+ * the kept permutation; the fp32 copy of the values, or the switch to or from it when their
+ * fp32-exactness changed; the SELL / BSELL value arrays, in place; d for LSPCG_PRECOND_DIAGONAL and
+ * _EXT_SPAI_SCALED.  Kept: the reverse Cuthill-McKee analysis, the SELL pattern, the split
+ * reductions' geometry, the vectors, stream and events.  LSPCG_PRECOND_IC with the factor computed
+ * here (lspcg_solver_set_ic): a numeric-only IC(0) into the existing factor, its transpose and the
+ * triangular solves' scaled values; the levels, padded orders and counter words are kept.  A given
+ * factor (lspcg_solver_set_ic_factor) and an installed ext_spai L are left alone: install the new L
+ * with lspcg_solver_set_spai.  The results are those of a solver created on the new values, bit for
+ * bit.  t_ms (nullable) = device time of the update; *graphs_kept (nullable) = 1 when the captured
+ * iteration graphs of lspcg_solver_solve and lspcg_solver_solve_multi survived, which they do exactly
+ * when no view moved or changed its storage type (0 across a change of fp32-exactness).  A call that
+ * returns an error has dropped the graphs (views may have moved before the failing step), and the
+ * successful call after it reports 0.
+ * LSPCG_ERR_BREAKDOWN from the numeric IC(0) (a non-positive pivot) leaves no usable factor: every
+ * solve returns LSPCG_ERR_BREAKDOWN until another lspcg_solver_update_matrix succeeds. */
+int lspcg_solver_update_matrix(lspcg_solver* s, double* t_ms, int* graphs_kept);
 /* Solve A x = b from x (x0, in/out).  Semantics of scipy.sparse.linalg.cg (iterative.py
  * 359-418): atol = rtol*||b||, ||r|| checked at the top of each iteration, iters = number
  * of completed iterations, max_iter <= 0 means n.  res_hist (host, nullable, length
@@ -315,6 +343,16 @@ int lspcg_tridiag_extremes(int64_t m, const double* diag, const double* off, dou
 int lspcg_assemble(lspcg_ctx* ctx, int64_t nb, int64_t E, int bs, const int64_t* edge_index,
                    const void* blocks, int in_dtype, const void* mask, int mask_dtype,
                    int out_dtype, int out_block, lspcg_mat** out);
+/* lspcg_assemble into an existing handle A (its dtype is the output dtype): the same masking and
+ * the same zero dropping, and the values are written only if the resulting rowptr / colind equal
+ * A's.  Otherwise -- another mask, a block value that became exactly 0 (scalar output drops it),
+ * another size -- LSPCG_ERR_FORMAT, and A is left bit for bit as it was.  No host copy of the
+ * pattern: the count pass's row pointer and the fill pass's columns land in scratch arrays that
+ * are compared with A's on the device, with one flag read.  A lspcg_mat_prepare_spmv copy is
+ * refilled as by lspcg_mat_set_values; the same rules for running solves and solvers apply. */
+int lspcg_assemble_into(lspcg_ctx* ctx, int64_t nb, int64_t E, int bs, const int64_t* edge_index,
+                        const void* blocks, int in_dtype, const void* mask, int mask_dtype,
+                        int out_block, lspcg_mat* A);
 
 /* ---- GNN (NodeEdgeProcessing, F = hidden = 16, FeedForward num_layers = 2) ---- */
 typedef struct lspcg_gnn_desc {

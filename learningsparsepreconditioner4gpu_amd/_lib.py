@@ -51,6 +51,7 @@ SIGNATURES = {
     "lspcg_mat_destroy": (C.c_int, [vp]),
     "lspcg_mat_info": (C.c_int, [vp, p_i64, p_i64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lspcg_mat_copy_out": (C.c_int, [vp, vp, vp, vp]),
+    "lspcg_mat_set_values": (C.c_int, [vp, vp, vp, vp, C.c_int]),
     "lspcg_mat_transpose": (C.c_int, [vp, pp]),
     "lspcg_mat_diagonal": (C.c_int, [vp, vp]),
     "lspcg_mat_rcm": (C.c_int, [vp, vp, C.POINTER(C.c_int), p_f64, p_f64]),
@@ -70,6 +71,7 @@ SIGNATURES = {
     "lspcg_solver_set_spai": (C.c_int, [vp, vp, C.c_double, p_f64]),
     "lspcg_solver_set_ic": (C.c_int, [vp, p_f64]),
     "lspcg_solver_set_ic_factor": (C.c_int, [vp, vp, p_f64]),
+    "lspcg_solver_update_matrix": (C.c_int, [vp, p_f64, C.POINTER(C.c_int)]),
     "lspcg_solver_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_int64, p_i64, p_f64, p_f64]),
     "lspcg_solver_solve_coef": (C.c_int, [vp, vp, vp, C.c_double, C.c_int64, p_i64, p_f64, p_f64, p_f64]),
     "lspcg_solver_solve_multi": (C.c_int, [vp, C.c_int, vp, vp, C.c_double, C.c_int64, p_i64, p_i32,
@@ -89,6 +91,7 @@ SIGNATURES = {
     "lspcg_tridiag_extremes": (C.c_int, [C.c_int64, p_f64, p_f64, p_f64, p_f64]),
     "lspcg_assemble": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int,
                                  C.c_int, pp]),
+    "lspcg_assemble_into": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]),
     "lspcg_gnn_create": (C.c_int, [vp, C.POINTER(lspcg_gnn_desc), vp, C.c_int64, pp]),
     "lspcg_gnn_set_graph": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
     "lspcg_gnn_forward": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, vp, vp]),

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <memory>
 #include <string>
 
@@ -179,9 +180,65 @@ static int grid_of(int64_t n) {
   return int(g < 1 ? 1 : (g > kElemBlocksMax ? kElemBlocksMax : g));
 }
 
+// lspcg_assemble_into: the same count / fill passes into scratch arrays, the resulting pattern compared with
+// `into`'s on the device (one flag read), the values copied over only when it is the same.  The
+// scratch holds the largest pattern the passes can write (every edge entry kept plus one inserted
+// diagonal per row), so the fill is in bounds whatever the mask and the values turned out to be.
+template <typename TO, typename TI, typename TM, int BS>
+static int assemble_into_t(lspcg_ctx* ctx, const AsmIn<TO, TI, TM>& in, int out_block, lspcg_mat* A, int* flag) {
+  hipStream_t st = ctx->stream;
+  const int64_t nb = in.nb, E = in.E, n = nb * BS;
+  LSPCG_CHECK(A->ctx == ctx && A->storage_dtype() == A->dtype, LSPCG_ERR_ARG, "assemble_into: a matrix of another context");
+  LSPCG_CHECK(A->block_size == (out_block ? BS : 1) && A->n == n, LSPCG_ERR_FORMAT,
+              "assemble_into: the matrix has another size or block size (nothing written)");
+  DevBuf B;
+  int32_t *rp = nullptr, *ci = nullptr;
+  TO* v = nullptr;
+  int hflag = 0;
+  if (out_block) {
+    if (int rc = B.get(&rp, nb + 1) | B.get(&ci, E) | B.get(&v, E * BS * BS)) return rc;
+    hipLaunchKernelGGL((k_asm_bsr<TO, TI, TM, BS>), dim3(grid_of(nb)), dim3(kThreads), 0, st, in, rp, ci, v, flag);
+    if (nb == 0) LSPCG_HIP(hipMemsetAsync(rp, 0, sizeof(int32_t), st));
+    pattern_neq(rp, A->rowptr, nb + 1, ci, A->colind, std::min(E, A->nnzb), flag, st);
+    LSPCG_HIP(hipGetLastError());
+    if (int rc = flag_value(flag, st, &hflag)) return rc;
+    LSPCG_CHECK(!(hflag & 4), LSPCG_ERR_FORMAT,
+                "assemble: BSR output needs the diagonal block of every Dirichlet-masked block row");
+    LSPCG_CHECK(!(hflag & 2) && E == A->nnzb, LSPCG_ERR_FORMAT,
+                "assemble_into: the assembled pattern differs from the matrix's (nothing written)");
+    if (E) LSPCG_HIP(hipMemcpyAsync(A->vals, v, sizeof(TO) * E * BS * BS, hipMemcpyDeviceToDevice, st));
+  } else {
+    const int64_t cap = E * BS * BS + n;
+    int32_t* cnt = nullptr;
+    if (int rc = B.get(&cnt, n + 1) | B.get(&rp, n + 1) | B.get(&ci, cap) | B.get(&v, cap)) return rc;
+    hipLaunchKernelGGL((k_asm_rows<TO, TI, TM, BS, false>), dim3(seg_grid(n)), dim3(256), 0, st, in,
+                       static_cast<const int32_t*>(nullptr), cnt, static_cast<int32_t*>(nullptr), static_cast<TO*>(nullptr));
+    LSPCG_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int32_t), st));
+    size_t tmp_bytes = 0;
+    LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt, rp, int(n + 1), st));
+    void* tmp = nullptr;
+    if (int rc = B.get(&tmp, tmp_bytes)) return rc;
+    LSPCG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, rp, int(n + 1), st));
+    hipLaunchKernelGGL((k_asm_rows<TO, TI, TM, BS, true>), dim3(seg_grid(n)), dim3(256), 0, st, in,
+                       static_cast<const int32_t*>(rp), static_cast<int32_t*>(nullptr), ci, v);
+    // equal row pointers give equal entry counts, so the columns are compared over A's (a differing
+    // row pointer raises the flag whatever the columns say)
+    pattern_neq(rp, A->rowptr, n + 1, ci, A->colind, std::min(cap, A->nnzb), flag, st);
+    LSPCG_HIP(hipGetLastError());
+    if (int rc = flag_value(flag, st, &hflag)) return rc;
+    LSPCG_CHECK(!(hflag & 2), LSPCG_ERR_FORMAT,
+                "assemble_into: the assembled pattern differs from the matrix's (nothing written)");
+    if (A->nnzb) LSPCG_HIP(hipMemcpyAsync(A->vals, v, sizeof(TO) * A->nnzb, hipMemcpyDeviceToDevice, st));
+  }
+  if (int rc = mat_refresh_spmv(A)) return rc;
+  LSPCG_HIP(hipStreamSynchronize(st));  // the scratch is freed on return
+  return LSPCG_OK;
+}
+
+// `into` (nullable): lspcg_assemble_into's existing handle, *out unused
 template <typename TO, typename TI, typename TM, int BS>
 static int assemble_t(lspcg_ctx* ctx, int64_t nb, int64_t E, const int64_t* ei, const void* blocks, const void* mask,
-                      int out_dtype, int out_block, lspcg_mat** out) {
+                      int out_dtype, int out_block, lspcg_mat** out, lspcg_mat* into) {
   hipStream_t st = ctx->stream;
   DevBuf B;
   int32_t* bptr = nullptr;
@@ -197,6 +254,7 @@ static int assemble_t(lspcg_ctx* ctx, int64_t nb, int64_t E, const int64_t* ei, 
               "assemble: edge_index must be row-major sorted without duplicates (make_bsr_from_coo_inds contract)");
   AsmIn<TO, TI, TM> in{nb, E, ei, static_cast<const TI*>(blocks), static_cast<const TM*>(mask), bptr};
   const int64_t n = nb * BS;
+  if (into) return assemble_into_t<TO, TI, TM, BS>(ctx, in, out_block, into, flag);
 
   std::unique_ptr<lspcg_mat, int (*)(lspcg_mat*)> m(new lspcg_mat(), lspcg_mat_destroy);
   m->ctx = ctx;
@@ -247,38 +305,52 @@ static int assemble_t(lspcg_ctx* ctx, int64_t nb, int64_t E, const int64_t* ei, 
 
 template <typename TO, typename TI, typename TM>
 static int assemble_bs(lspcg_ctx* ctx, int64_t nb, int64_t E, int bs, const int64_t* ei, const void* blocks,
-                       const void* mask, int out_dtype, int out_block, lspcg_mat** out) {
-  if (bs == 1) return assemble_t<TO, TI, TM, 1>(ctx, nb, E, ei, blocks, mask, out_dtype, out_block, out);
-  if (bs == 3) return assemble_t<TO, TI, TM, 3>(ctx, nb, E, ei, blocks, mask, out_dtype, out_block, out);
+                       const void* mask, int out_dtype, int out_block, lspcg_mat** out, lspcg_mat* into) {
+  if (bs == 1) return assemble_t<TO, TI, TM, 1>(ctx, nb, E, ei, blocks, mask, out_dtype, out_block, out, into);
+  if (bs == 3) return assemble_t<TO, TI, TM, 3>(ctx, nb, E, ei, blocks, mask, out_dtype, out_block, out, into);
   set_error("assemble: block size must be 1 or 3");
   return LSPCG_ERR_UNSUPPORTED;
 }
 
 template <typename TO, typename TI>
 static int assemble_m(lspcg_ctx* ctx, int64_t nb, int64_t E, int bs, const int64_t* ei, const void* blocks,
-                      const void* mask, int mask_dtype, int out_dtype, int out_block, lspcg_mat** out) {
+                      const void* mask, int mask_dtype, int out_dtype, int out_block, lspcg_mat** out, lspcg_mat* into) {
   if (mask_dtype == LSPCG_F32)
-    return assemble_bs<TO, TI, float>(ctx, nb, E, bs, ei, blocks, mask, out_dtype, out_block, out);
-  return assemble_bs<TO, TI, double>(ctx, nb, E, bs, ei, blocks, mask, out_dtype, out_block, out);
+    return assemble_bs<TO, TI, float>(ctx, nb, E, bs, ei, blocks, mask, out_dtype, out_block, out, into);
+  return assemble_bs<TO, TI, double>(ctx, nb, E, bs, ei, blocks, mask, out_dtype, out_block, out, into);
 }
 
 }  // namespace lspcg
 
 using namespace lspcg;
 
-extern "C" int lspcg_assemble(lspcg_ctx* ctx, int64_t nb, int64_t E, int bs, const int64_t* edge_index,
-                              const void* blocks, int in_dtype, const void* mask, int mask_dtype, int out_dtype,
-                              int out_block, lspcg_mat** out) {
-  LSPCG_CHECK(ctx && out && (E == 0 || (edge_index && blocks)), LSPCG_ERR_ARG, "assemble: NULL argument");
+static int assemble_any(lspcg_ctx* ctx, int64_t nb, int64_t E, int bs, const int64_t* edge_index, const void* blocks,
+                        int in_dtype, const void* mask, int mask_dtype, int out_dtype, int out_block, lspcg_mat** out,
+                        lspcg_mat* into) {
+  LSPCG_CHECK(ctx && (out || into) && (E == 0 || (edge_index && blocks)), LSPCG_ERR_ARG, "assemble: NULL argument");
   LSPCG_CHECK(nb >= 0 && E >= 0 && nb * bs < (int64_t(1) << 31) && E < (int64_t(1) << 31), LSPCG_ERR_ARG,
               "assemble: sizes out of range");
   LSPCG_HIP(hipSetDevice(ctx->device));
   if (out_dtype == LSPCG_F64) {
     if (in_dtype == LSPCG_F32)
-      return assemble_m<double, float>(ctx, nb, E, bs, edge_index, blocks, mask, mask_dtype, out_dtype, out_block, out);
-    return assemble_m<double, double>(ctx, nb, E, bs, edge_index, blocks, mask, mask_dtype, out_dtype, out_block, out);
+      return assemble_m<double, float>(ctx, nb, E, bs, edge_index, blocks, mask, mask_dtype, out_dtype, out_block, out, into);
+    return assemble_m<double, double>(ctx, nb, E, bs, edge_index, blocks, mask, mask_dtype, out_dtype, out_block, out, into);
   }
   if (in_dtype == LSPCG_F32)
-    return assemble_m<float, float>(ctx, nb, E, bs, edge_index, blocks, mask, mask_dtype, out_dtype, out_block, out);
-  return assemble_m<float, double>(ctx, nb, E, bs, edge_index, blocks, mask, mask_dtype, out_dtype, out_block, out);
+    return assemble_m<float, float>(ctx, nb, E, bs, edge_index, blocks, mask, mask_dtype, out_dtype, out_block, out, into);
+  return assemble_m<float, double>(ctx, nb, E, bs, edge_index, blocks, mask, mask_dtype, out_dtype, out_block, out, into);
+}
+
+extern "C" int lspcg_assemble(lspcg_ctx* ctx, int64_t nb, int64_t E, int bs, const int64_t* edge_index,
+                              const void* blocks, int in_dtype, const void* mask, int mask_dtype, int out_dtype,
+                              int out_block, lspcg_mat** out) {
+  LSPCG_CHECK(out, LSPCG_ERR_ARG, "assemble: NULL argument");
+  return assemble_any(ctx, nb, E, bs, edge_index, blocks, in_dtype, mask, mask_dtype, out_dtype, out_block, out, nullptr);
+}
+
+extern "C" int lspcg_assemble_into(lspcg_ctx* ctx, int64_t nb, int64_t E, int bs, const int64_t* edge_index,
+                                   const void* blocks, int in_dtype, const void* mask, int mask_dtype, int out_block,
+                                   lspcg_mat* A) {
+  LSPCG_CHECK(A, LSPCG_ERR_ARG, "assemble_into: NULL matrix");
+  return assemble_any(ctx, nb, E, bs, edge_index, blocks, in_dtype, mask, mask_dtype, A->dtype, out_block, nullptr, A);
 }

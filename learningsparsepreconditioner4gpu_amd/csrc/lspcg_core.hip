@@ -184,6 +184,21 @@ static int grid_for(int64_t n) {
   return int(std::max<int64_t>(1, std::min<int64_t>(g, kElemBlocksMax)));
 }
 
+// flag |= 2 when a[0..n) != b[0..n): streaming, coalesced, one atomic per wave that saw a difference
+__global__ void __launch_bounds__(kThreads) k_pattern_neq(int64_t n, const int32_t* __restrict__ a,
+                                                          const int32_t* __restrict__ b, int* __restrict__ flag) {
+  bool bad = false;
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x)
+    bad |= a[i] != b[i];
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 2);
+}
+
+void pattern_neq(const int32_t* rp_a, const int32_t* rp_b, int64_t nrp, const int32_t* ci_a, const int32_t* ci_b,
+                 int64_t nci, int* flag, hipStream_t st) {
+  if (nrp > 0) launch(k_pattern_neq, dim3(grid_for(nrp)), dim3(kThreads), st, nrp, rp_a, rp_b, flag);
+  if (nci > 0) launch(k_pattern_neq, dim3(grid_for(nci)), dim3(kThreads), st, nci, ci_a, ci_b, flag);
+}
+
 // diagnostic gather: one 16-B load of an interleaved pair, a - alpha*b (the fused schedule's
 // r - alpha q / p beta + z gathers with the two vectors interleaved)
 struct GatherPairDiag {
@@ -450,6 +465,72 @@ int lspcg::mat_transpose(const lspcg_mat* A, lspcg_mat** out, bool* same_pattern
   LSPCG_HIP(hipStreamSynchronize(st));
   guard.release();
   *out = Tm;
+  return LSPCG_OK;
+}
+
+int lspcg::mat_refresh_spmv(lspcg_mat* A) {
+  SellCopy* c = A->sell;
+  if (!c) return LSPCG_OK;
+  hipStream_t st = A->ctx->stream;
+  const lspcg_mat* M = A;
+  if (c->ro.perm) {  // the kept permutation: P A Pᵀ overwritten in place (the pattern reads its rowptr)
+    lspcg_mat* out = nullptr;
+    if (int rc = mat_permute(A, c->ro, &out, c->Ap)) return rc;
+    if (out != c->Ap) {
+      lspcg_mat_destroy(out);
+      set_error("set_values: the permuted copy of the SpMV analysis does not fit the matrix");
+      return LSPCG_ERR_ARG;
+    }
+    M = c->Ap;
+  }
+  const int vd = M->storage_dtype();
+  return c->P.bs == 3 ? bsell_fill_values(c->P, M->vals, vd, vd, st, &c->vals)
+                      : sell_fill_values(c->P, M->colind, M->vals, vd, vd, st, &c->vals);
+}
+
+// a pointer the device can read as it is (hipMalloc'd); anything else is staged by a copy
+static bool is_device_pointer(const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();  // an unregistered host pointer: not an error of ours
+    return false;
+  }
+  return at.type == hipMemoryTypeDevice;
+}
+
+extern "C" int lspcg_mat_set_values(lspcg_mat* A, const int32_t* indptr, const int32_t* indices, const void* vals,
+                                    int dtype) {
+  LSPCG_CHECK(A && (vals || A->nnzb == 0), LSPCG_ERR_ARG, "set_values: NULL argument");
+  LSPCG_CHECK(dtype == A->dtype && A->storage_dtype() == A->dtype, LSPCG_ERR_ARG,
+              "set_values: the values' dtype differs from the matrix dtype");
+  LSPCG_HIP(hipSetDevice(A->ctx->device));
+  hipStream_t st = A->ctx->stream;
+  if (indptr || indices) {  // the pattern the values belong to: compared on the device before any write
+    DevBuf B;
+    int* flag = nullptr;
+    if (int rc = B.get(&flag, 1)) return rc;
+    LSPCG_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+    auto on_device = [&](const int32_t* p, int64_t n, const int32_t** out) -> int {
+      *out = p;
+      if (!p || n == 0 || is_device_pointer(p)) return LSPCG_OK;
+      int32_t* d = nullptr;
+      if (int rc = B.get(&d, n)) return rc;
+      LSPCG_HIP(hipMemcpyAsync(d, p, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+      *out = d;
+      return LSPCG_OK;
+    };
+    const int32_t *rp = nullptr, *ci = nullptr;
+    if (int rc = on_device(indptr, A->nb + 1, &rp) | on_device(indices, A->nnzb, &ci)) return rc;
+    pattern_neq(rp, A->rowptr, rp ? A->nb + 1 : 0, ci, A->colind, ci ? A->nnzb : 0, flag, st);
+    LSPCG_HIP(hipGetLastError());
+    int f = 0;
+    if (int rc = flag_value(flag, st, &f)) return rc;
+    LSPCG_CHECK(!f, LSPCG_ERR_FORMAT, "set_values: indptr / indices differ from the matrix's pattern (nothing written)");
+  }
+  const int64_t ne = A->nnzb * A->block_size * A->block_size;
+  if (ne) LSPCG_HIP(hipMemcpyAsync(A->vals, vals, dtype_size(dtype) * ne, hipMemcpyDefault, st));
+  if (int rc = mat_refresh_spmv(A)) return rc;
+  LSPCG_HIP(hipStreamSynchronize(st));  // host sources may be released by the caller
   return LSPCG_OK;
 }
 

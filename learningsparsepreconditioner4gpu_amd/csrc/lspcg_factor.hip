@@ -310,8 +310,15 @@ __device__ __forceinline__ U trsv_poll(const U* p) {
   return __hip_atomic_load(const_cast<U*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// (also resets the block dequeue counter head[0] for the launch that follows.  Observed with the reset
+// as a hipMemsetAsync node between the kernel nodes of the iteration graph: once other work with a
+// host read had run on the context's stream between two solves, replays gave NaN from the second
+// triangular solve on, until a device-wide synchronize or a re-capture; with the reset here they do
+// not.  Supposed, not shown: the node was no longer ordered before the launch, so the counter still
+// held the previous solve's value, every workgroup left at once and x kept the wait pattern.)
 template <typename T>
-__global__ void k_trsv_wait_fill(int64_t n, T* __restrict__ x, const int32_t* done) {
+__global__ void k_trsv_wait_fill(int64_t n, T* __restrict__ x, const int32_t* done, unsigned* head) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(head, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (done && *done) return;
   using U = typename TrsvBits<T>::U;
   for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x)
@@ -457,6 +464,20 @@ int trsv_plan_build(const lspcg_mat* T_, bool lower, TrsvPlan* out) {
     out->sv = B.keep(sv);
     out->inv = B.keep(inv);
     out->c = B.keep(c);
+    return trsv_plan_refill(T_, lower, *out);
+  });
+  if (rc) out->release();
+  return rc;
+}
+
+int trsv_plan_refill(const lspcg_mat* T_, bool lower, const TrsvPlan& plan) {
+  hipStream_t st = T_->ctx->stream;
+  const int64_t n = T_->n, nnz = T_->nnzb;
+  if (n == 0) return LSPCG_OK;
+  LSPCG_CHECK(plan.sv && plan.inv && plan.c, LSPCG_ERR_ARG, "trsv: no plan to refill");
+  return by_dtype(T_->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    T *sv = as<T>(plan.sv), *inv = as<T>(plan.inv), *c = as<T>(plan.c);
     by_flag(lower, [&](auto lo) {
       launch(k_trsv_inv<T, decltype(lo)::value>, dim3(fgrid(n)), dim3(kThreads), st, n, T_->rowptr, as<T>(T_->vals),
              inv, c);
@@ -465,8 +486,6 @@ int trsv_plan_build(const lspcg_mat* T_, bool lower, TrsvPlan* out) {
     LSPCG_HIP(hipGetLastError());
     return LSPCG_OK;
   });
-  if (rc) out->release();
-  return rc;
 }
 
 int enqueue_trsv(const lspcg_mat* T_, const TrsvPlan& plan, bool lower, const void* b, void* x, const int32_t* done,
@@ -475,10 +494,9 @@ int enqueue_trsv(const lspcg_mat* T_, const TrsvPlan& plan, bool lower, const vo
   const int64_t n = T_->n;
   // 1 workgroup per CU (2 or 4 measured slower: more polling waves)
   const dim3 g(unsigned(std::min<int64_t>((plan.npad + 255) / 256, int64_t(plan.cus)))), blk(256);
-  LSPCG_HIP(hipMemsetAsync(plan.head, 0, sizeof(unsigned), st));
   by_dtype(T_->dtype, [&](auto t) {
     using T = decltype(t);
-    launch(k_trsv_wait_fill<T>, dim3(fgrid(n)), dim3(kThreads), st, n, as<T>(x), done);
+    launch(k_trsv_wait_fill<T>, dim3(fgrid(n)), dim3(kThreads), st, n, as<T>(x), done, plan.head);
     by_flag(lower, [&](auto lo) {
       constexpr bool LOWER = decltype(lo)::value;
       launch(k_trsv_syncfree<T, LOWER>, g, blk, st, plan.npad, plan.pad, T_->rowptr, T_->colind, as<T>(plan.sv),
@@ -505,14 +523,9 @@ int trsv_check_timeout(const TrsvPlan& plan, hipStream_t st) {
   return LSPCG_OK;
 }
 
-int ic0_factor(const lspcg_mat* A, lspcg_mat** out) {
-  LSPCG_CHECK(A && out, LSPCG_ERR_ARG, "ic0: NULL");
-  hipStream_t st = A->ctx->stream;
-  lspcg_mat* L = nullptr;
-  if (int rc = tril_of(A, true, &L)) return rc;
-  MatGuard guard(L, lspcg_mat_destroy);
-  Levels lv;
-  if (int rc = build_levels(A->ctx, L->n, L->rowptr, L->colind, true, &lv)) return rc;
+// the level launches of IC(0) on L = tril(A)'s values; LSPCG_ERR_BREAKDOWN on a non-positive pivot
+static int ic0_levels(lspcg_mat* L, const Levels& lv) {
+  hipStream_t st = L->ctx->stream;
   DevBuf B;
   int* flag = nullptr;
   if (int rc = B.get(&flag, 1)) return rc;
@@ -530,8 +543,36 @@ int ic0_factor(const lspcg_mat* A, lspcg_mat** out) {
   if (int rc = flag_value(flag, st, &f)) return rc;
   LSPCG_CHECK(!f, LSPCG_ERR_BREAKDOWN,
               "IC(0) breakdown: a non-positive pivot (the matrix is not an M-matrix / not SPD)");
+  return LSPCG_OK;
+}
+
+int ic0_factor(const lspcg_mat* A, lspcg_mat** out, Levels* levels) {
+  LSPCG_CHECK(A && out, LSPCG_ERR_ARG, "ic0: NULL");
+  lspcg_mat* L = nullptr;
+  if (int rc = tril_of(A, true, &L)) return rc;
+  MatGuard guard(L, lspcg_mat_destroy);
+  Levels own;
+  Levels& lv = levels ? *levels : own;
+  if (int rc = build_levels(A->ctx, L->n, L->rowptr, L->colind, true, &lv)) return rc;
+  if (int rc = ic0_levels(L, lv)) return rc;
   *out = guard.release();
   return LSPCG_OK;
+}
+
+int ic0_numeric(const lspcg_mat* A, lspcg_mat* L, const Levels& lv) {
+  LSPCG_CHECK(A && L, LSPCG_ERR_ARG, "ic0: NULL");
+  LSPCG_CHECK(A->block_size == 1 && L->block_size == 1 && A->n == L->n && A->dtype == L->dtype &&
+                  int64_t(lv.hptr.size()) == int64_t(lv.nlev) + 1 && (L->n == 0 || lv.hptr.back() == L->n),
+              LSPCG_ERR_ARG, "ic0_numeric: L and its levels do not belong to A");
+  hipStream_t st = A->ctx->stream;
+  // L <- tril(A)'s values at L's row pointers (the columns it rewrites are the ones L has)
+  by_dtype(A->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_tril_fill<T>, dim3(fgrid(A->n)), dim3(kThreads), st, A->n, A->rowptr, A->colind, as<T>(A->vals), L->rowptr,
+           L->colind, as<T>(L->vals));
+  });
+  LSPCG_HIP(hipGetLastError());
+  return ic0_levels(L, lv);
 }
 
 // ---------------------------------------------------------------------------

@@ -45,16 +45,24 @@ struct TrsvPlan {
 
 // levels of T, their padded order, the counter words and T's scaled values (replaces *out)
 int trsv_plan_build(const lspcg_mat* T, bool lower, TrsvPlan* out);
+// New values in T, same pattern: sv / inv / c recomputed in place (enqueued, not waited for).  The
+// levels, the padded order and the counter words depend on the pattern alone and are kept.
+int trsv_plan_refill(const lspcg_mat* T, bool lower, const TrsvPlan& plan);
 // x = T⁻¹ b in scipy spsolve_triangular's arithmetic (lower: diagonal stored last in each row,
 // upper: first); `done` (nullable) is the solver's device done flag -- every launch returns at
 // once when it is set.  Counter reset + fill + one sync-free launch (rows wait for their
-// dependencies' values) + the diagonal scaling.
+// dependencies' values) + the diagonal scaling: three kernel launches, no memset or copy node.
 int enqueue_trsv(const lspcg_mat* T, const TrsvPlan& plan, bool lower, const void* b, void* x, const int32_t* done,
                  hipStream_t st);
-constexpr int kTrsvLaunches = 4;  // graph nodes one enqueue_trsv adds
+constexpr int kTrsvLaunches = 3;  // graph nodes one enqueue_trsv adds
 // LSPCG_ERR_HIP (and clears the flag) when a sync-free solve with this plan timed out
 int trsv_check_timeout(const TrsvPlan& plan, hipStream_t st);
-int ic0_factor(const lspcg_mat* A, lspcg_mat** L);
+// levels (nullable) <- the level sets of L's rows, for ic0_numeric
+int ic0_factor(const lspcg_mat* A, lspcg_mat** L, Levels* levels = nullptr);
+// Numeric-only IC(0): L (an ic0_factor result for a matrix of A's pattern) <- the factor of A's
+// current values, with ic0_factor's kernels in its order (the same bits).  On LSPCG_ERR_BREAKDOWN
+// L holds no usable factor.
+int ic0_numeric(const lspcg_mat* A, lspcg_mat* L, const Levels& levels);
 int ainv0_factor(const lspcg_mat* A, lspcg_mat** L);
 
 }  // namespace lspcg

@@ -581,6 +581,13 @@ int flag_value(const int* dflag, hipStream_t st, int* out);
 // not taken: *out != reuse)
 int mat_transpose(const lspcg_mat* A, lspcg_mat** out, bool* same_pattern, lspcg_mat* reuse);
 bool mat_reusable(const lspcg_mat* old, const lspcg_mat* like);
+// Enqueue the comparison of two patterns: *flag |= 2 when rp_a[0..nrp) != rp_b[0..nrp) or
+// ci_a[0..nci) != ci_b[0..nci) (device arrays; the caller zeroes and reads the flag)
+void pattern_neq(const int32_t* rp_a, const int32_t* rp_b, int64_t nrp, const int32_t* ci_a, const int32_t* ci_b,
+                 int64_t nci, int* flag, hipStream_t st);
+// A's values were overwritten in place: refill the lspcg_mat_prepare_spmv copy (pattern, kind and
+// permutation kept); nothing to do without one
+int mat_refresh_spmv(lspcg_mat* A);
 
 // Bandwidth-reducing row placement (lspcg_reorder.hip): perm[i'] = original (block) row of row
 // i', iperm its inverse (device arrays, nb entries); off_* = mean |col - row| of the pattern in the

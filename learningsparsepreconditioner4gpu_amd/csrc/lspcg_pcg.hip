@@ -148,6 +148,26 @@ static int build_sell_bsr3(lspcg_solver* s, int w, const lspcg_mat* view) {
   return LSPCG_OK;
 }
 
+// New values in A's iteration view, same pattern (lspcg_solver_update_matrix): the SELL / BSELL
+// value array is refilled in place, or allocated anew when the view's storage type changed (values
+// that became, or stopped being, fp32-exact).  The pattern is never rebuilt.
+static int refill_sell_A(lspcg_solver* s) {
+  const SellPattern* P = s->sp[0];
+  if (!P) return LSPCG_OK;  // the staged CSR / BSR kernel reads the view itself
+  const int vd = s->Av.storage_dtype();
+  if (s->sv[0] && (vd != s->svd[0] || s->svn[0] != P->slots())) {
+    (void)hipFree(s->sv[0]);
+    s->sv[0] = nullptr;
+  }
+  hipStream_t st = s->ctx->stream;
+  const int rc = P->bs == 3 ? bsell_fill_values(*P, s->Av.vals, vd, vd, st, &s->sv[0])
+                            : sell_fill_values(*P, s->Av.colind, s->Av.vals, vd, vd, st, &s->sv[0]);
+  if (rc) return rc;
+  s->svd[0] = vd;
+  s->svn[0] = P->slots();
+  return LSPCG_OK;
+}
+
 static int flag_run(lspcg_solver* s, hipStream_t st, int* out) {
   int h = 0;
   LSPCG_HIP(hipMemcpyAsync(&h, s->flag, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -425,7 +445,7 @@ static int setup_A(lspcg_solver* s) {
       s->A = s->Ap;
     }
   }
-  if (int rc = make_view(s, s->A, &s->Av, nullptr, &s->own_A)) return rc;
+  if (int rc = make_view(s, s->A, &s->Av, nullptr, &s->own_A, nullptr, nullptr, &s->own_A_n)) return rc;
   if (int rc = build_sell(s, 0, &s->Av)) return rc;
   setup_split_cg(s);
   if (s->precond == LSPCG_PRECOND_DIAGONAL) {
@@ -533,6 +553,18 @@ static GraphKey graph_key(const lspcg_solver* s) {
   put(s->gsz_a);
   put(s->ng_a);
   put(s->dot_order);
+  for (const lspcg_mat* T : {s->icL, s->icU}) {  // the triangular solves' operands (IC)
+    put(T ? T->rowptr : nullptr);
+    put(T ? T->colind : nullptr);
+  }
+  for (const TrsvPlan* pl : {&s->planL, &s->planU}) {
+    put(pl->pad);
+    put(pl->npad);
+    put(pl->head);
+    put(pl->sv);
+    put(pl->inv);
+    put(pl->c);
+  }
   k.eps = s->eps;
   return k;
 }
@@ -652,7 +684,9 @@ static int install_ic(lspcg_solver* s, const lspcg_mat* given, double* t_prec_ms
   s->planU.release();
   int rc = given ? lspcg_mat_create_csr(s->ctx, given->n, given->nnzb, given->rowptr, given->colind, given->vals,
                                         given->dtype, &s->icL)
-                 : ic0_factor(s->A, &s->icL);
+                 : ic0_factor(s->A, &s->icL, &s->ic_lev);
+  s->ic_own = !given;
+  s->ic_broken = false;
   if (!rc) rc = lspcg_mat_transpose(s->icL, &s->icU);
   if (!rc) rc = trsv_plan_build(s->icL, true, &s->planL);
   if (!rc) rc = trsv_plan_build(s->icU, false, &s->planU);
@@ -668,6 +702,78 @@ static int install_ic(lspcg_solver* s, const lspcg_mat* given, double* t_prec_ms
 }
 
 int lspcg_solver_set_ic(lspcg_solver* s, double* t_prec_ms) { return install_ic(s, nullptr, t_prec_ms); }
+
+// lspcg_solver_update_matrix's steps; any error return leaves views that may have moved
+static int update_matrix_steps(lspcg_solver* s) {
+  int rc = LSPCG_OK;
+  if (s->ro.perm) {  // P A Pᵀ with the kept permutation, over the previous one
+    lspcg_mat* out = nullptr;
+    if ((rc = mat_permute(s->A_user, s->ro, &out, s->Ap))) return rc;
+    if (out != s->Ap) {  // (the SELL pattern and the L views read Ap's index arrays)
+      lspcg_mat_destroy(out);
+      set_error("update_matrix: the solver's matrix no longer has the shape it was created with");
+      return LSPCG_ERR_FORMAT;
+    }
+  }
+  // the fp32 copy refilled in place, or the switch to / from it when the values' fp32-exactness changed
+  if ((rc = make_view(s, s->A, &s->Av, nullptr, &s->own_A, nullptr, nullptr, &s->own_A_n))) return rc;
+  if ((rc = refill_sell_A(s))) return rc;
+  if (s->precond == LSPCG_PRECOND_DIAGONAL || s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED) {
+    if ((rc = solver_diagonal(s))) return rc;
+  }
+  if (s->precond == LSPCG_PRECOND_IC && s->icL && s->ic_own) {
+    // numeric-only IC(0) into icL, its transpose into icU, the plans' scaled values; the levels, the
+    // padded orders and the counter words belong to the pattern
+    s->ic_broken = true;
+    if ((rc = ic0_numeric(s->A, s->icL, s->ic_lev))) return rc;
+    lspcg_mat* keep = s->icU;
+    s->icU = nullptr;
+    rc = mat_transpose(s->icL, &s->icU, nullptr, keep);
+    if (keep && keep != s->icU) lspcg_mat_destroy(keep);
+    if (rc) return rc;
+    if ((rc = trsv_plan_refill(s->icL, true, s->planL))) return rc;
+    if ((rc = trsv_plan_refill(s->icU, false, s->planU))) return rc;
+    s->ic_broken = false;
+  }
+  return LSPCG_OK;
+}
+
+int lspcg_solver_update_matrix(lspcg_solver* s, double* t_ms, int* graphs_kept) {
+  LSPCG_CHECK(s, LSPCG_ERR_ARG, "update_matrix: NULL");
+  LSPCG_HIP(hipSetDevice(s->ctx->device));
+  if (graphs_kept) *graphs_kept = 0;
+  hipStream_t cst = s->ctx->stream;
+  const GraphKey key_before = graph_key(s);
+  LSPCG_HIP(hipStreamSynchronize(s->stream));  // a running solve reads everything rewritten below
+  // From here the views may move (the fp32 copy, a SELL value array of another storage type): a
+  // failed update -- an IC(0) breakdown, an allocation -- drops the graphs, which hold the old
+  // addresses by value, and the update that follows it reports none kept.
+  const bool after_failure = s->update_failed;
+  s->update_failed = true;
+  auto fail = [&](int rc) {
+    s->graphs.clear();
+    multi_clear_graphs(s);
+    return rc;
+  };
+  if (hipEventRecord(s->ev_t0, cst) != hipSuccess) return fail(LSPCG_ERR_HIP);
+  if (int rc = update_matrix_steps(s)) return fail(rc);
+  float ms = 0.f;
+  if (hipEventRecord(s->ev_t1, cst) != hipSuccess || hipEventSynchronize(s->ev_t1) != hipSuccess ||
+      hipEventElapsedTime(&ms, s->ev_t0, s->ev_t1) != hipSuccess) {
+    set_error("update_matrix: timing the update on the context's stream failed");
+    return fail(LSPCG_ERR_HIP);
+  }
+  if (t_ms) *t_ms = ms;
+  s->update_failed = false;
+  // graphs hold the views' addresses and kinds by value: they survive exactly when none moved
+  const bool kept = !after_failure && graph_key(s) == key_before;
+  if (!kept) {
+    s->graphs.clear();
+    multi_clear_graphs(s);
+  }
+  if (graphs_kept) *graphs_kept = kept ? 1 : 0;
+  return LSPCG_OK;
+}
 
 int lspcg_solver_set_ic_factor(lspcg_solver* s, const lspcg_mat* L, double* t_prec_ms) {
   LSPCG_CHECK(L, LSPCG_ERR_ARG, "set_ic_factor: NULL factor");
@@ -685,6 +791,8 @@ int lspcg_solver_solve_coef(lspcg_solver* s, const void* b, void* x, double rtol
   LSPCG_CHECK(!(s->precond == LSPCG_PRECOND_EXT_SPAI || s->precond == LSPCG_PRECOND_EXT_SPAI_SCALED) || s->LT,
               LSPCG_ERR_ARG, "solve: ext_spai not set");
   LSPCG_CHECK(s->precond != LSPCG_PRECOND_IC || s->icL, LSPCG_ERR_ARG, "solve: IC factor not set (lspcg_solver_set_ic)");
+  LSPCG_CHECK(!s->ic_broken, LSPCG_ERR_BREAKDOWN,
+              "solve: the last lspcg_solver_update_matrix broke down in IC(0); update the matrix again first");
   LSPCG_HIP(hipSetDevice(s->ctx->device));
   const int64_t n = s->n;
   if (max_iter <= 0) max_iter = n;

@@ -112,12 +112,18 @@ struct lspcg_solver {
   void* own_A = nullptr;
   void* own_L = nullptr;
   void* own_LT = nullptr;
-  int64_t own_L_n = -1, own_LT_n = -1;  // entries of the fp32 copies above (refilled in place)
+  int64_t own_A_n = -1, own_L_n = -1, own_LT_n = -1;  // entries of the fp32 copies above (refilled in place)
   int* flag = nullptr;
   // IC(0): factor, its explicit transpose and their sync-free solve plans
   lspcg_mat* icL = nullptr;
   lspcg_mat* icU = nullptr;
   lspcg::TrsvPlan planL, planU;
+  // lspcg_solver_update_matrix: the level sets of icL's rows (set_ic's own factor; a given factor
+  // does not follow A), and whether a numeric refactorization broke down and left icL unusable
+  lspcg::Levels ic_lev;
+  bool ic_own = false;
+  bool ic_broken = false;
+  bool update_failed = false;  // the last lspcg_solver_update_matrix returned an error (its graphs were dropped)
   // SELL-64 copies of the scalar iteration views A (0), L (1), Lᵀ (2) (lspcg_sell.hpp); sp[w]
   // is null where the CSR kernel is used (block size 3, irregular rows, LSPCG_NO_SELL=1)
   bool use_sell = true;

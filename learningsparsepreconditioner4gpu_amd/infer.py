@@ -186,7 +186,8 @@ def _rhs(rhs: str, i: int, s: GraphSample, rhs_vectors: Optional[Dict[int, np.nd
 
 def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: float = 1e-6, repeat: int = 1,
         rhs: str = "mask", warmup: int = 20, concurrency: int = 1, batch: int = 1, dot_order: str = "compensated",
-        dot_threads: int = 1, rhs_vectors: Optional[Dict[int, np.ndarray]] = None) -> List[SolveRecord]:
+        dot_threads: int = 1, rhs_vectors: Optional[Dict[int, np.ndarray]] = None, reuse_solver: bool = False,
+        solutions: Optional[Dict[int, torch.Tensor]] = None) -> List[SolveRecord]:
     """The ``Neural+CUDA`` row of infer.py:278-331 (GNN -> L, A; ext_spai PCG).  ``concurrency``
     > 1 keeps that many solves of this rank in flight at once (run_sharded_concurrent): the same
     iterates and counts, a higher batch throughput on the reference's mid-size systems.  ``batch``
@@ -196,9 +197,17 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
     window's graphs (workspace.inference_step_batch): the same L, counts and iterates, every launch
     covering the whole window; a record's t_prec / t_solve are its shares of the window's forward
     / device solve time.  ``dot_order`` / ``dot_threads``: the loop's dot order (``"openblas"`` =
-    parity mode; not with ``batch`` > 1, whose lockstep schedule has the compensated order only)."""
+    parity mode; not with ``batch`` > 1, whose lockstep schedule has the compensated order only).
+    ``reuse_solver`` (opt-in; fixed-topology datasets, one solve at a time): one solver per
+    preconditioner kind and sample shape is kept across samples -- a sample's A is assembled into the
+    solver's matrix (``system_matrix(out=)``) and installed with ``update_matrix``, its L with the
+    in-place ``set_spai`` -- instead of the reference's one solver per repeat; a sample whose pattern
+    differs (``ERR_FORMAT``) gets a fresh solver, which is kept in turn.  The same counts and iterates.
+    ``solutions`` (optional dict): receives sample i's last iterate under key i."""
     if batch > 1 and dot_order != "compensated":
         raise ValueError("batch > 1 runs the compensated dot order only; use batch=1 for dot_order='openblas'")
+    if reuse_solver and (batch > 1 or concurrency > 1):
+        raise ValueError("reuse_solver keeps one solver across samples: one solve at a time (batch=1, concurrency=1)")
     scaled = isinstance(ws, ScaledInferenceWorkspace)
     pcg = get_pcg_scaled_iter_time if scaled else get_pcg_iter_time
     pcg_batch = get_pcg_scaled_iter_time_batch if scaled else get_pcg_iter_time_batch
@@ -221,11 +230,63 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
         r = _rhs(rhs, i, s, rhs_vectors)
         return i, A, L, r, prec
 
+    kept = {}  # reuse_solver: (kind, n, nnzb, block size) -> the solver of that shape (it owns its A)
+
+    def solve_reusing(i: int) -> SolveRecord:
+        from . import _lib
+        from .linalg import PreconditionedConjugateGradient
+        from .validate import _device_rhs, relative_residual
+
+        s = samples[i].to(dev)
+        if not warmed:
+            for _ in range(warmup):
+                ws.inference_step(s)
+            warmed.add(True)
+        prec = 0.0
+        for _ in range(repeat):
+            _, dt = ws.inference_step(s)
+            prec += dt
+        prec /= repeat
+        L, _ = ws.inference_step(s)
+        kind = "ext_spai_scaled" if scaled else "ext_spai"
+        solver = None
+        for key, cand in kept.items():
+            if key[:2] != (kind, L.n) or key[3] != L.block_size:
+                continue
+            try:
+                ws.system_matrix(s, out=cand.A)
+            except _lib.LspcgError as e:
+                if e.code != _lib.ERR_FORMAT:
+                    raise
+                continue  # another pattern: cand.A is unchanged
+            cand.update_matrix()
+            solver = cand
+            break
+        if solver is None:
+            A = ws.system_matrix(s)
+            solver = PreconditionedConjugateGradient(A, device="cuda", preconditioner=kind, dtype=np.float64,
+                                                     dot_order=dot_order, dot_threads=dot_threads)
+            kept[(kind, A.n, A.nnzb, A.block_size)] = solver
+        A = solver.A
+        b = _device_rhs(A, _rhs(rhs, i, s, rhs_vectors))
+        it_sum, sol = 0, 0.0
+        for _ in range(repeat):
+            xs = torch.zeros_like(b)
+            it, _, dt = solver(b.clone(), xs, rtol, A.n, ext_spai=(L, ws.epsilon))
+            it_sum += it
+            sol += dt
+        if solutions is not None:
+            solutions[i] = xs
+        return SolveRecord(index=i, iters=it_sum / repeat, rel_res=relative_residual(A, xs, b), t_prec=prec,
+                           t_solve=sol / repeat, n=A.n, nnz=A.nnz, converged=bool(solver.last_converged))
+
     def finish(job) -> SolveRecord:
         i, A, L, r, prec = job
         info = {}
         it, _, sol = pcg(A, r, L, ws.epsilon, rtol=rtol, repeat=repeat, device="cuda", info=info,
                          dot_order=dot_order, dot_threads=dot_threads)
+        if solutions is not None:
+            solutions[i] = info["x"]
         # the true ‖b − A x‖/‖b‖ of the solution (one device SpMV) and the solver's own verdict
         return SolveRecord(index=i, iters=it, rel_res=info["rel_res"], t_prec=prec, t_solve=sol, n=A.n, nnz=A.nnz,
                            converged=info["converged"])
@@ -259,6 +320,8 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
         return run_sharded_batched(len(samples), weights, prepare, finish_batch, batch, prepare_batch=prepare_batch)
     if concurrency > 1:
         return run_sharded_concurrent(len(samples), weights, prepare, finish, concurrency)
+    if reuse_solver:
+        return run_sharded(len(samples), weights, solve_reusing)
     return run_sharded(len(samples), weights, lambda i: finish(prepare(i)))
 
 
@@ -404,6 +467,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=1,
                     help="systems per lockstep batch per GPU (run_sharded_batched) for the Neural row (either "
                          "workspace) and the none / diagonal / ainv baselines; 1 = one solve at a time")
+    ap.add_argument("--reuse-solver", action="store_true",
+                    help="with --fixed-topology: keep one solver per sample shape for the Neural row and install each "
+                         "sample's A and L on it in place (update_matrix) instead of one solver per repeat")
     ap.add_argument("--baselines", default="none,diagonal,ainv,ic",
                     help="comma list of PCG-{method}-cuda rows (infer.py:310-321); '' for none")
     ap.add_argument("--dot-order", default="compensated", choices=["compensated", "openblas"],
@@ -421,6 +487,8 @@ def main(argv=None):
 
     import torch.distributed as dist
 
+    if args.reuse_solver and not (args.folder and args.fixed_topology):
+        ap.error("--reuse-solver needs --folder with --fixed-topology (samples that share one pattern)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # one GPU per local rank; more ranks than GPUs (a gloo rehearsal on one GPU) share them
@@ -456,7 +524,8 @@ def main(argv=None):
                                              rhs_vectors=rhs_vectors, batch=args.batch, **dots)
     key = "Neural+HIP" if args.hip_key else "Neural+CUDA"
     rows[key] = run(samples, ws, rtol=args.rtol, repeat=args.repeat, rhs=args.rhs, warmup=args.warmup,
-                    concurrency=args.concurrency, batch=args.batch, rhs_vectors=rhs_vectors, **dots)
+                    concurrency=args.concurrency, batch=args.batch, rhs_vectors=rhs_vectors,
+                    reuse_solver=args.reuse_solver, **dots)
     recs = rows[key]
     if args.cpu_rows and (not dist.is_initialized() or dist.get_rank() == 0):
         rows.update(run_cpu_rows(samples, ws, rtol=args.rtol, repeat=args.repeat, rhs=args.rhs,

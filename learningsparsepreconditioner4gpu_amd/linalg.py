@@ -67,6 +67,16 @@ def _as_device_matrix(M, dtype, block_size: int, ctx: Context) -> DeviceMatrix:
     return DeviceMatrix.from_scipy(sp.csr_matrix(M), dtype=dtype, block_size=block_size, ctx=ctx)
 
 
+def _copy_values(dst: DeviceMatrix, src: DeviceMatrix) -> None:
+    """``dst.set_values`` from ``src`` on the device, ``src``'s pattern checked against ``dst``'s."""
+    dev = dst.ctx.torch_device
+    ip = torch.empty(src.n // src.block_size + 1, dtype=torch.int32, device=dev)
+    ix = torch.empty(src.nnzb, dtype=torch.int32, device=dev)
+    v = torch.empty(src.nnz, dtype=src.dtype, device=dev)
+    _lib.call("lspcg_mat_copy_out", src.handle, _ptr(ip), _ptr(ix), _ptr(v))
+    dst.set_values(v, indptr=ip, indices=ix)
+
+
 MULTI_RHS_MAX = 8  # right-hand sides of one lspcg_solver_solve_multi call
 
 
@@ -78,6 +88,9 @@ def _rhs_groups(k: int):
 
 
 class PreconditionedConjugateGradient:
+    A = None  # (class defaults: an object whose __init__ has not run holds no matrix to go stale)
+    _A_values = 0
+
     def __new__(cls, matrix=None, device: str = "cuda", preconditioner: str = "none", dtype=np.float64,
                 block_size: int = 1, ctx: Optional[Context] = None, dot_order: str = "compensated",
                 dot_threads: int = 1):
@@ -113,6 +126,7 @@ class PreconditionedConjugateGradient:
         self.handle = h
         self._L = None
         self._spai_key = None
+        self._A_values = self.A.values_version  # the values of self.A the native solver was set up on
         self.dot_order = ("compensated", 1)
         self.setup_time = 0.0  # device setup of the ic / ainv preconditioner (seconds)
         if preconditioner == "ic":
@@ -141,6 +155,78 @@ class PreconditionedConjugateGradient:
             raise
         self.setup_time = ms.value / 1e3
         return self.setup_time
+
+    def update_matrix(self, A_new=None) -> Tuple[float, bool]:
+        """New values of A on this solver, same pattern (``lspcg_solver_update_matrix``): returns
+        ``(setup_time_s, graphs_kept)``.  ``A_new=None``: ``self.A`` was changed in place
+        (``DeviceMatrix.set_values``, ``sparse.assemble(out=)``); a scipy matrix or a ``DeviceMatrix`` of
+        the same pattern is copied into ``self.A`` through the checked ``set_values`` first -- another
+        pattern raises ``LspcgError`` (``ERR_FORMAT``), another dtype ``TypeError``, and the solver then
+        still solves the old system.  Only what depends on the values is redone (DESIGN.md "New values
+        of A"); the next solves give a fresh solver's bits.  ``"ic"`` refactors numerically (a given
+        ``set_ic_factor`` factor is left alone), ``"ainv"`` recomputes its factor and installs it in
+        place; an ``ext_spai`` factor stays until the next ``set_spai`` / ``ext_spai=``.
+        ``graphs_kept``: the captured iteration graphs survived (always, unless the values'
+        fp32-exactness changed, or the update before this one failed).  A breakdown of the numeric
+        IC(0) or of AINV(0) raises ``LspcgError`` (``ERR_BREAKDOWN``); the solver's solves then raise
+        until another update succeeds."""
+        if A_new is not None and A_new is not self.A:
+            if isinstance(A_new, DeviceMatrix):
+                if A_new.dtype_code != self.A.dtype_code:
+                    raise TypeError(f"matrix dtype {A_new.dtype} differs from solver dtype {self.dtype}")
+                if (A_new.n, A_new.nnzb, A_new.block_size) != (self.A.n, self.A.nnzb, self.A.block_size):
+                    raise _lib.LspcgError(_lib.ERR_FORMAT, "update_matrix: the new matrix has another size, entry count "
+                                                           "or block size (nothing written)")
+                _copy_values(self.A, A_new)
+            else:
+                if not sp.issparse(A_new):
+                    raise TypeError(f"A_new must be a scipy sparse matrix or a DeviceMatrix, got {type(A_new).__name__}")
+                if np.dtype(A_new.dtype) != self.dtype:
+                    raise TypeError(f"matrix dtype {A_new.dtype} differs from solver dtype {self.dtype}")
+                bs = self.A.block_size
+                if bs == 1:
+                    M = sp.csr_matrix(A_new)
+                    if not M.has_sorted_indices:
+                        M = M.sorted_indices()
+                else:
+                    if isinstance(A_new, sp.bsr_matrix) and A_new.blocksize == (bs, bs):
+                        M = A_new
+                        if not M.has_sorted_indices:  # sort a copy: the caller's matrix keeps its order
+                            M = M.copy()
+                            M.sort_indices()
+                    else:
+                        M = sp.bsr_matrix(sp.csr_matrix(A_new), blocksize=(bs, bs))
+                        M.sort_indices()
+                if M.shape != self.A.shape or M.indices.size != self.A.nnzb:
+                    raise _lib.LspcgError(_lib.ERR_FORMAT, "update_matrix: the new matrix has another size or entry "
+                                                           "count (nothing written)")
+                self.A.set_values(np.ascontiguousarray(M.data, dtype=self.dtype).reshape(-1),
+                                  indptr=np.ascontiguousarray(M.indptr, dtype=np.int32),
+                                  indices=np.ascontiguousarray(M.indices, dtype=np.int32))
+        if self.preconditioner == "ainv":
+            # before the native update: a breakdown of AINV(0) then leaves this solver behind self.A's
+            # values, and its solves raise (naming update_matrix) instead of pairing the new A with the old factor
+            L, tf = self.A.ainv0()
+        ms, kept = C.c_double(), C.c_int()
+        _lib.call("lspcg_solver_update_matrix", self.handle, C.byref(ms), C.byref(kept))
+        self._A_values = self.A.values_version
+        t = ms.value / 1e3
+        if self.preconditioner == "ainv":
+            if self._L is not None and (self._L.n, self._L.nnzb) == (L.n, L.nnzb):
+                # into the installed factor's handle (AINV(0)'s pattern is tril(A)'s): the views keep
+                # their addresses, so set_spai keeps the graphs as well
+                _copy_values(self._L, L)
+                L = self._L
+            t += tf + self.set_spai(L, 0.0)
+            self._spai_key = ("ainv",)
+        if self.preconditioner in ("ic", "ainv"):
+            self.setup_time = t
+        return t, bool(kept.value)
+
+    def _check_matrix_current(self):
+        if self.A is not None and self.A.values_version != self._A_values:
+            raise RuntimeError("the values of this solver's matrix changed in place (set_values / assemble(out=)): "
+                               "call update_matrix() before solving")
 
     def set_dot_order(self, order: str = "compensated", threads: int = 1):
         """Summation order of the loop's dots and norms (include/lspcg.h lspcg_solver_set_dot_order).
@@ -192,11 +278,15 @@ class PreconditionedConjugateGradient:
     def _key(L, epsilon):
         """Identity of an installed ext_spai factor: the object itself (held, so its id cannot be
         reused by another object), its in-place version (DeviceMatrix) and ε."""
-        return (L, getattr(L, "version", None), float(epsilon))
+        return (L, PreconditionedConjugateGradient._version(L), float(epsilon))
+
+    @staticmethod
+    def _version(L):
+        return (getattr(L, "version", None), getattr(L, "values_version", None))
 
     def _is_installed(self, L, epsilon) -> bool:
         k = self._spai_key
-        return (k is not None and len(k) == 3 and k[0] is L and k[1] == getattr(L, "version", None)
+        return (k is not None and len(k) == 3 and k[0] is L and k[1] == self._version(L)
                 and k[2] == float(epsilon))
 
     def solve(self, b: torch.Tensor, x: torch.Tensor, rtol: float = 1e-6, max_iter: int = 0,
@@ -205,6 +295,7 @@ class PreconditionedConjugateGradient:
         ``return_coefficients``: the loop's own scalars ρ_k = r_k·z_k and π_k = p_k·q_k of the ``iters``
         completed iterations (``lspcg_solver_solve_coef``) -- the Lanczos coefficients of M⁻¹A that
         :mod:`.spectrum` turns into its extreme eigenvalues.  The solve itself is the same, bit for bit."""
+        self._check_matrix_current()
         self._check_vector("b", b)
         self._check_vector("x", x)
         mi = int(max_iter) if max_iter and max_iter > 0 else self.n
@@ -243,6 +334,7 @@ class PreconditionedConjugateGradient:
         ``ext_spai`` / ``ext_spai_scaled`` / ``ainv`` solvers of scalar systems with SELL-DIA or
         SELL-64 views (:attr:`views`: ``sdia``, ``sell16``, ``sell32``) in the compensated dot order;
         anything else raises ``LspcgError`` with code ``ERR_UNSUPPORTED``."""
+        self._check_matrix_current()
         self._check_block("B", B)
         self._check_block("X", X)
         if B.shape != X.shape:
@@ -317,6 +409,7 @@ class PreconditionedConjugateGradient:
 
     def __call__(self, b, x, rtol: float = 1e-6, max_iter: int = 0, ext_spai=None,
                  return_history: bool = False) -> Tuple:
+        self._check_matrix_current()
         prec = self.setup_time
         if self.preconditioner in ("ext_spai", "ext_spai_scaled"):
             if ext_spai is None and self._L is None:

@@ -80,6 +80,9 @@ class DeviceMatrix:
         _lib.call("lspcg_mat_info", handle, C.byref(n), C.byref(nnzb), C.byref(bs), C.byref(dt))
         self.n, self.nnzb, self.block_size, self.dtype_code = n.value, nnzb.value, bs.value, dt.value
         self.version = 0  # bumped by in-place value changes (solvers key their installed L on it)
+        # bumped by set_values / assemble(out=): a solver created on this matrix refuses to solve
+        # until its update_matrix has seen the new values (its own counter, so `version` keeps its meaning)
+        self.values_version = 0
 
     # ---- construction
     @classmethod
@@ -157,6 +160,42 @@ class DeviceMatrix:
             return sp.csr_matrix((vals, indices, indptr), shape=self.shape)
         b = self.block_size
         return sp.bsr_matrix((vals.reshape(-1, b, b), indices, indptr), shape=self.shape, blocksize=(b, b))
+
+    def set_values(self, vals, indptr=None, indices=None) -> "DeviceMatrix":
+        """New values on the same pattern (``lspcg_mat_set_values``): ``vals`` -- a numpy array or a
+        tensor of the matrix dtype with ``nnzb * block_size**2`` entries in the stored order --
+        overwrites the values in place.  ``indptr`` / ``indices`` (optional, int32) are compared with
+        the matrix's on the device first; a difference raises ``LspcgError`` (``ERR_FORMAT``) and
+        nothing is written.  A :meth:`prepare_spmv` copy is refilled in place.  Solvers created on
+        this matrix need ``update_matrix()`` before their next solve."""
+        def arr(a, want, count, name):
+            if isinstance(a, torch.Tensor):
+                if a.dtype != want[0]:
+                    raise TypeError(f"{name} is {a.dtype}, expected {want[0]}")
+                if a.is_cuda and a.device != self.ctx.torch_device:
+                    raise ValueError(f"{name} is on {a.device}, the matrix is on {self.ctx.torch_device}")
+                a = a.contiguous().reshape(-1)
+                n, ptr = a.numel(), C.c_void_p(a.data_ptr())
+            else:
+                a = np.asarray(a)
+                if a.dtype != np.dtype(want[1]):
+                    raise TypeError(f"{name} is {a.dtype}, expected {np.dtype(want[1])}")
+                a = np.ascontiguousarray(a).reshape(-1)
+                n, ptr = a.size, a.ctypes.data_as(C.c_void_p)
+            if n != count and name != "vals":  # another pattern: refused as the device comparison refuses it
+                raise _lib.LspcgError(_lib.ERR_FORMAT, f"set_values: {name} has {n} entries, the matrix's has {count} "
+                                                       "(nothing written)")
+            if n != count:
+                raise ValueError(f"{name} has {n} entries, the matrix stores {count}")
+            return a, ptr
+
+        i32 = (torch.int32, np.int32)
+        keep = [arr(vals, (_TORCH[self.dtype_code], _NP[self.dtype_code]), self.nnz, "vals")]
+        keep.append(arr(indptr, i32, self.n // self.block_size + 1, "indptr") if indptr is not None else (None, None))
+        keep.append(arr(indices, i32, self.nnzb, "indices") if indices is not None else (None, None))
+        _lib.call("lspcg_mat_set_values", self.handle, keep[1][1], keep[2][1], keep[0][1], self.dtype_code)
+        self.values_version += 1
+        return self
 
     def transpose(self) -> "DeviceMatrix":
         h = C.c_void_p()
@@ -253,13 +292,30 @@ def dot(x: torch.Tensor, y: torch.Tensor, ctx: Optional[Context] = None) -> floa
 
 
 def assemble(edge_index: torch.Tensor, blocks: torch.Tensor, n: int, mask: Optional[torch.Tensor] = None,
-             dtype=torch.float64, block_output: bool = False, ctx: Optional[Context] = None) -> DeviceMatrix:
+             dtype=torch.float64, block_output: bool = False, ctx: Optional[Context] = None,
+             out: Optional[DeviceMatrix] = None) -> DeviceMatrix:
     """``to_csr_cpu`` on the GPU (validate.py:22-51): COO block edges -> masked CSR/BSR in HBM.
 
     ``blocks`` is ``[E]`` / ``[E,1,1]`` (scalar) or ``[E,b,b]``; ``n`` is the scalar size.
     ``block_output=False`` reproduces to_csr_cpu exactly (scalar CSR, zeros dropped);
     ``block_output=True`` keeps b x b blocks for the BSR kernels.
+
+    ``out``: an existing matrix of the same pattern (a fixed mesh with new coefficients) whose values
+    are overwritten in place (``lspcg_assemble_into``) and which is returned; its dtype is the output
+    dtype.  The same masking and zero dropping run, and if the resulting pattern is not ``out``'s --
+    another mask, a block value that became exactly 0 -- ``LspcgError`` (``ERR_FORMAT``) is raised and
+    ``out`` is unchanged.  Solvers created on ``out`` need ``update_matrix()`` before their next solve.
     """
+    if out is not None:
+        if not isinstance(out, DeviceMatrix):
+            raise TypeError(f"out must be a DeviceMatrix, got {type(out).__name__}")
+        if ctx is not None and ctx is not out.ctx:
+            raise ValueError("out belongs to another context")
+        if out.n != n:
+            raise ValueError(f"out has {out.n} rows, n is {n}")
+        if out.block_size != (blocks.shape[-1] if block_output and blocks.ndim == 3 else 1):
+            raise ValueError(f"out has block size {out.block_size}, block_output={block_output} asks for another")
+        ctx = out.ctx
     ctx = ctx or Context.get(blocks.device if blocks.is_cuda else None)
     dev = ctx.torch_device
     if blocks.ndim == 1:
@@ -278,6 +334,11 @@ def assemble(edge_index: torch.Tensor, blocks: torch.Tensor, n: int, mask: Optio
             m = m.double()
         mcode = lspcg_dtype(m.dtype)
         assert m.numel() == n
+    if out is not None:
+        _lib.call("lspcg_assemble_into", ctx.handle, n // bs, ei.shape[1], bs, _ptr(ei), _ptr(bl),
+                  lspcg_dtype(bl.dtype), _ptr(m) if m is not None else None, mcode, int(block_output), out.handle)
+        out.values_version += 1
+        return out
     h = C.c_void_p()
     _lib.call("lspcg_assemble", ctx.handle, n // bs, ei.shape[1], bs, _ptr(ei), _ptr(bl), lspcg_dtype(bl.dtype),
               _ptr(m) if m is not None else None, mcode, lspcg_dtype(dtype), int(block_output), C.byref(h))

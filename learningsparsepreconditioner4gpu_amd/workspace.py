@@ -264,10 +264,11 @@ class SimpleInferenceWorkspace:
 
         return save_checkpoint(self, path, epoch=epoch, global_step=global_step, optimizer=optimizer, hparams=hparams)
 
-    def _assemble(self, sample: GraphSample, boo: torch.Tensor, block_output: Optional[bool]) -> DeviceMatrix:
+    def _assemble(self, sample: GraphSample, boo: torch.Tensor, block_output: Optional[bool],
+                  out: Optional[DeviceMatrix] = None) -> DeviceMatrix:
         n = sample.num_nodes * self.block_size
         bo = (self.block_size > 1) if block_output is None else block_output
-        return assemble(sample.edge_index, boo, n, sample.mask, dtype=torch.float64, block_output=bo)
+        return assemble(sample.edge_index, boo, n, sample.mask, dtype=torch.float64, block_output=bo, out=out)
 
     # ---- workspace.py:195-205
     def inference_step(self, sample: GraphSample, time_beg: Optional[float] = None, block_output: Optional[bool] = None,
@@ -309,10 +310,14 @@ class SimpleInferenceWorkspace:
             e0 += E
         return Ls, dt
 
-    def system_matrix(self, sample: GraphSample, block_output: Optional[bool] = None) -> DeviceMatrix:
-        """``to_csr_cpu(edge_index, matrix_values, n, mask)`` (infer.py:282) on the device."""
+    def system_matrix(self, sample: GraphSample, block_output: Optional[bool] = None,
+                      out: Optional[DeviceMatrix] = None) -> DeviceMatrix:
+        """``to_csr_cpu(edge_index, matrix_values, n, mask)`` (infer.py:282) on the device.  ``out``: a
+        matrix of the same pattern (an earlier sample of a fixed-topology dataset) to overwrite in place
+        (``sparse.assemble(out=)``: ``LspcgError`` with ``ERR_FORMAT``, ``out`` unchanged, when the
+        pattern differs)."""
         s = sample if sample.x.is_cuda else sample.to(self.device)
-        return self._assemble(s, s.matrix_values, block_output)
+        return self._assemble(s, s.matrix_values, block_output, out=out)
 
 
     def condition_number(self, sample: GraphSample, kind: str = "neural", **kw):
