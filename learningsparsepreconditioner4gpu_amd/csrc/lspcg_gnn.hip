@@ -126,7 +126,11 @@ struct FragRegs {
   }
 };
 
-// layers 2 and 3 of an FF on the layer-1 pre-activation `h` (in accumulator layout)
+// layers 2 and 3 of an FF on the layer-1 pre-activation `h` (in accumulator layout).  BIAS_LAST: the
+// output layer's bias is added after the products, not accumulated onto (the fp32-MFMA decoder: its
+// bias is the bulk of an output whose edge-to-edge variation is a few percent of it, and four MFMA
+// steps rounded at the bias's magnitude cost up to 3 ulp of that output)
+template <bool BIAS_LAST = false>
 __device__ __forceinline__ f4 ff_tail(const float* fr, int s1, f4 h, int lane) {
   const float* a2 = fr + s1 * 64 + 256;
   const float* c2 = a2 + 256;
@@ -137,9 +141,11 @@ __device__ __forceinline__ f4 ff_tail(const float* fr, int s1, f4 h, int lane) {
 #pragma unroll
   for (int s = 0; s < 4; ++s) h2 = mfma(a2[s * 64 + lane], comp(h, s), h2);
   h2 = gelu4(h2);
-  f4 o = *reinterpret_cast<const f4*>(c3 + lane * 4);
+  const f4 b3 = *reinterpret_cast<const f4*>(c3 + lane * 4);
+  f4 o = BIAS_LAST ? f4{0.f, 0.f, 0.f, 0.f} : b3;
 #pragma unroll
   for (int s = 0; s < 4; ++s) o = mfma(a3[s * 64 + lane], comp(h2, s), o);
+  if constexpr (BIAS_LAST) o += b3;
   return o;
 }
 
@@ -473,12 +479,12 @@ __device__ __forceinline__ f4 ff_tile_regs(const FragRegs<S1>& w, const float (&
   return o;
 }
 
-template <int S1>
+template <int S1, bool BIAS_LAST = false>
 __device__ __forceinline__ f4 ff_tile(const float* fr, const float (&in)[S1], int lane) {
   f4 h = *reinterpret_cast<const f4*>(fr + S1 * 64 + lane * 4);
 #pragma unroll
   for (int s = 0; s < S1; ++s) h = mfma(fr[s * 64 + lane], in[s], h);
-  return ff_tail(fr, S1, h, lane);
+  return ff_tail<BIAS_LAST>(fr, S1, h, lane);
 }
 
 
@@ -648,7 +654,7 @@ __global__ void __launch_bounds__(256) k_edge_dec(int64_t E, const float* __rest
     float in[12];
     pack12(ld4(ecsc + int64_t(inv[ee]) * H + 4 * q), ld4(x + int64_t(ra[ee]) * H + 4 * q), ld4(x + int64_t(rb[ee]) * H + 4 * q), in);
     f4 o;
-    if constexpr (F32) o = ff_tile<12>(wd, in, lane);
+    if constexpr (F32) o = ff_tile<12, true>(wd, in, lane);
     else o = ff1_48(wd, in, lane, us);
     if (valid) {
 #pragma unroll

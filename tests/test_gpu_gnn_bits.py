@@ -6,7 +6,8 @@ reach every branch of the packed-blob layout and of the fragment packer, with th
 library chose and the hidden bound it reports.  The hashes were recorded with this file's
 ``__main__`` block on the commit the fixture names; the Python API it drives (``build_gnn``,
 forward, ``_backward``) is the same there, so a refactor of the layout / packer code has to
-reproduce them exactly.
+reproduce them exactly.  The ``out`` hashes of the four fp32 cases were recorded again when the
+fp32-MFMA decoder began to add its bias after the products (``fp32_out_recorded_from``).
 
     python tests/test_gpu_gnn_bits.py --commit <sha> [--out tests/golden/gnn_bits.json]
 
