@@ -318,6 +318,33 @@ int lspcg_batch_solve(lspcg_batch* bt, const void* const* b, void* const* x, dou
 int lspcg_batch_solve_coef(lspcg_batch* bt, const void* const* b, void* const* x, double rtol, int64_t max_iter,
                            int64_t* iters, int32_t* status, double* const* res_hist, double* t_solve_ms,
                            double* const* coef);
+/* New values of A and / or L on a live batch, same patterns (the next window of an is_fixed_topology
+ * folder, the next time step on fixed meshes).  A, L: arrays of nsys handles; either array may be
+ * NULL (those values stay) and any entry may be NULL (that system's matrix stays); L must be NULL
+ * for none / diagonal batches.  epsilon replaces the batch's (ignored for none / diagonal).  The
+ * handles are read during the call only.
+ * Checked on the host before any launch: a given matrix of another dtype, or L given to a batch that
+ * takes none, is LSPCG_ERR_ARG; another block size, size or entry count is LSPCG_ERR_FORMAT.  Then
+ * ONE launch compares every given rowptr / colind with the system's slice of the block-diagonal
+ * copy and one flag is read back: any difference in any system is LSPCG_ERR_FORMAT and nothing has
+ * been written -- not the systems before the offending one, not any L -- so the batch still solves
+ * its old systems, bit for bit.
+ * After the checks one launch copies all given values into the block-diagonal copies in place, the
+ * batch's stream is drained, and what depends on values is redone on the internal solver: for a new A
+ * what lspcg_solver_update_matrix redoes (the fp32 copy of the values or the switch to or from it,
+ * the SELL / BSELL value arrays in place, d for LSPCG_PRECOND_DIAGONAL and _EXT_SPAI_SCALED, 1 on
+ * padding rows), for a new L or epsilon what lspcg_solver_set_spai redoes (L^T and the views of L
+ * and L^T, in place).  Kept: the block-diagonal patterns, the SELL patterns, the tile maps, tickets,
+ * partials, states, stream and events, the one-workgroup / lockstep and sums / tickets decisions.
+ * The results are those of a batch created on the resulting matrices, bit for bit.
+ * t_ms (nullable) = device time of the update, checks included; *graphs_kept (nullable) = 1 when the
+ * captured iteration graphs of lspcg_batch_solve survived, which they do exactly when no view moved
+ * or changed its storage type and epsilon is the same (0 across a change of the concatenated
+ * values' fp32-exactness, or of epsilon).  A call that fails after its checks (an allocation, a HIP
+ * error) has dropped the graphs; solves return that error until an update succeeds, and that update
+ * reports graphs_kept = 0. */
+int lspcg_batch_update(lspcg_batch* bt, const lspcg_mat* const* A, const lspcg_mat* const* L,
+                       double epsilon, double* t_ms, int* graphs_kept);
 int lspcg_batch_destroy(lspcg_batch* bt);
 
 /* ---- spectrum of the preconditioned system from the PCG scalars (host only: no device call) ----

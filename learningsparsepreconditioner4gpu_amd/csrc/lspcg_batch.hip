@@ -407,6 +407,49 @@ __global__ void k_cat_colind(int64_t nnz, const int32_t* __restrict__ c, int32_t
     out[k] = c[k] + off;
 }
 
+
+// One given matrix of an update window (lspcg_batch_update): the caller's arrays beside the
+// system's slice of the block-diagonal copy, which holds the pattern shifted by the system's entry
+// offset e0 (rowptr) and block-row offset brow (colind): k_cat_rowptr / k_cat_colind
+struct CatSlice {
+  const int32_t* rp;   // [nb + 1] the caller's
+  const int32_t* ci;   // [nnzb]
+  const void* vals;    // [nval]
+  const int32_t* crp;  // the slice of Acat / Lcat
+  const int32_t* cci;
+  void* cvals;
+  int64_t nb, nnzb, nval;  // block rows, stored blocks, values (bs * bs per block)
+  int32_t e0, brow;
+};
+
+// every given matrix of the window against its slice, matrices over gridDim.y: any difference sets
+// the flag (rows past nb of a slice are empty and repeat rowptr[nb]; they hold no caller's data)
+__global__ void __launch_bounds__(kThreads) k_cat_same_pattern(int nmat, const CatSlice* __restrict__ tab,
+                                                               int* __restrict__ flag) {
+  for (int m = blockIdx.y; m < nmat; m += gridDim.y) {
+    const CatSlice d = tab[m];
+    const int64_t nr = d.nb + 1, tot = nr + d.nnzb;
+    bool diff = false;
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < tot; i += int64_t(gridDim.x) * blockDim.x) {
+      if (i < nr) diff |= uint32_t(d.rp[i]) + uint32_t(d.e0) != uint32_t(d.crp[i]);
+      else diff |= uint32_t(d.ci[i - nr]) + uint32_t(d.brow) != uint32_t(d.cci[i - nr]);
+    }
+    if (diff) atomicOr(flag, 1);
+  }
+}
+
+// the given matrices' values into their slices, in place
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_cat_copy_values(int nmat, const CatSlice* __restrict__ tab) {
+  for (int m = blockIdx.y; m < nmat; m += gridDim.y) {
+    const CatSlice d = tab[m];
+    const T* __restrict__ src = static_cast<const T*>(d.vals);
+    T* __restrict__ dst = static_cast<T*>(d.cvals);
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < d.nval; i += int64_t(gridDim.x) * blockDim.x)
+      dst[i] = src[i];
+  }
+}
+
 }  // namespace lspcg
 
 struct lspcg_batch {
@@ -442,6 +485,13 @@ struct lspcg_batch {
   double* dhist = nullptr;
   int64_t dhist_cap = 0;
   lspcg::IterationGraphs graphs;  // of enqueue_batch_iteration
+  // lspcg_batch_update: every system's block rows and stored blocks of A and L, its entry offsets in
+  // Acat / Lcat, the descriptor table of one update (allocated by the first) and its timing events
+  std::vector<int64_t> nb, brow, annz, lnnz, ae0, le0;
+  lspcg::CatSlice* utab = nullptr;
+  hipEvent_t ev_u0 = nullptr, ev_u1 = nullptr;
+  bool update_failed = false;  // the last lspcg_batch_update failed past its checks: solves return update_rc
+  int update_rc = LSPCG_OK;
 };
 
 namespace lspcg {
@@ -580,6 +630,19 @@ static int cat_matrices(lspcg_ctx* ctx, int nsys, const lspcg_mat* const* M, con
   return LSPCG_OK;
 }
 
+// d = diag of the block-diagonal system (solver_create / set_spai / update_matrix) gets 1 on padding rows
+static int pad_d(lspcg_batch* bt) {
+  by_dtype(bt->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(k_batch_pad_d<T>, dim3(unsigned(bt->ntot / kThreads)), dim3(kThreads), bt->ctx->stream, batch_map(bt),
+           bt->boff, bt->bn, as<T>(bt->s->d));
+    return 0;
+  });
+  LSPCG_HIP(hipGetLastError());
+  LSPCG_HIP(hipStreamSynchronize(bt->ctx->stream));
+  return LSPCG_OK;
+}
+
 }  // namespace lspcg
 
 extern "C" {
@@ -596,6 +659,9 @@ int lspcg_batch_destroy(lspcg_batch* bt) {
                   (void*)bt->dhist})
     (void)hipFree(v);
   (void)hipHostFree(bt->hS);
+  (void)hipFree(bt->utab);
+  if (bt->ev_u0) (void)hipEventDestroy(bt->ev_u0);
+  if (bt->ev_u1) (void)hipEventDestroy(bt->ev_u1);
   delete bt;
   return LSPCG_OK;
 }
@@ -640,7 +706,15 @@ int lspcg_batch_create_precond(lspcg_ctx* ctx, int nsys, const lspcg_mat* const*
   for (int k = 0; k < nsys; ++k) {
     bt->off.push_back(brow[k] * bt->bs);
     bt->n.push_back(A[k]->n);
+    bt->nb.push_back(A[k]->nb);
+    bt->ae0.push_back(k ? bt->ae0[k - 1] + bt->annz[k - 1] : 0);
+    bt->annz.push_back(A[k]->nnzb);
+    if (spai) {
+      bt->le0.push_back(k ? bt->le0[k - 1] + bt->lnnz[k - 1] : 0);
+      bt->lnnz.push_back(L[k]->nnzb);
+    }
   }
+  bt->brow = brow;
   bt->ntot = brow[nsys] * bt->bs;
   if (int rc = cat_matrices(ctx, nsys, A, brow, &bt->Acat)) return rc;
   if (spai)
@@ -726,21 +800,119 @@ int lspcg_batch_create_precond(lspcg_ctx* ctx, int nsys, const lspcg_mat* const*
     LSPCG_HIP(hipMemcpy(bt->boff, ho.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
     LSPCG_HIP(hipMemcpy(bt->bn, hn.data(), sizeof(int32_t) * nsys, hipMemcpyHostToDevice));
   }
-  if (needs_d) {  // d = diag of the block-diagonal system (solver_create / set_spai), 1 on padding rows
-    by_dtype(bt->dtype, [&](auto t) {
-      using T = decltype(t);
-      launch(k_batch_pad_d<T>, dim3(unsigned(netiles)), dim3(kThreads), ctx->stream, batch_map(bt.get()), bt->boff,
-             bt->bn, as<T>(bt->s->d));
-      return 0;
-    });
-    LSPCG_HIP(hipGetLastError());
-    LSPCG_HIP(hipStreamSynchronize(ctx->stream));
-  }
+  if (needs_d)
+    if (int rc = pad_d(bt.get())) return rc;
   LSPCG_HIP(hipMalloc(&bt->tickets, sizeof(unsigned) * kTicketStride * lines));
   LSPCG_HIP(hipMemset(bt->tickets, 0, sizeof(unsigned) * kTicketStride * lines));
   LSPCG_HIP(hipMalloc(&bt->S, sizeof(PcgState) * nsys));
   LSPCG_HIP(hipHostMalloc(&bt->hS, 2 * sizeof(PcgState) * nsys, hipHostMallocDefault));
   *out = bt.release();
+  return LSPCG_OK;
+}
+
+int lspcg_batch_update(lspcg_batch* bt, const lspcg_mat* const* A, const lspcg_mat* const* L, double epsilon,
+                       double* t_ms, int* graphs_kept) {
+  LSPCG_CHECK(bt, LSPCG_ERR_ARG, "batch_update: NULL");
+  if (graphs_kept) *graphs_kept = 0;
+  const bool spai = bt->precond == LSPCG_PRECOND_EXT_SPAI || bt->precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
+  const bool needs_d = bt->precond == LSPCG_PRECOND_DIAGONAL || bt->precond == LSPCG_PRECOND_EXT_SPAI_SCALED;
+  LSPCG_CHECK(spai || !L, LSPCG_ERR_ARG, "batch_update: L must be NULL for none / diagonal");
+  if (!spai) epsilon = bt->s->eps;
+  const int ns = bt->nsys;
+  const int64_t bb = int64_t(bt->bs) * bt->bs;
+  std::vector<CatSlice> tab;
+  bool anyA = false, anyL = false;
+  for (int pass = 0; pass < 2; ++pass) {  // every A, then every L
+    const lspcg_mat* const* M = pass ? L : A;
+    if (!M) continue;
+    const lspcg_mat* C = pass ? bt->Lcat : bt->Acat;
+    const std::vector<int64_t>& nnz = pass ? bt->lnnz : bt->annz;
+    const std::vector<int64_t>& e0 = pass ? bt->le0 : bt->ae0;
+    const std::string what = std::string("batch_update: ") + (pass ? "L" : "A") + " of system ";
+    for (int k = 0; k < ns; ++k) {
+      const lspcg_mat* m = M[k];
+      if (!m) continue;
+      LSPCG_CHECK(m->dtype == bt->dtype && m->storage_dtype() == bt->dtype, LSPCG_ERR_ARG,
+                  what + std::to_string(k) + " has another dtype than the batch");
+      LSPCG_CHECK(m->block_size == bt->bs && m->n == bt->n[k] && m->nb == bt->nb[k] && m->nnzb == nnz[k],
+                  LSPCG_ERR_FORMAT,
+                  what + std::to_string(k) + " has another block size, size or entry count (nothing written)");
+      tab.push_back(CatSlice{m->rowptr, m->colind, m->vals, C->rowptr + bt->brow[k], C->colind + e0[k],
+                             static_cast<char*>(C->vals) + esize(bt->dtype) * size_t(bb) * size_t(e0[k]), m->nb,
+                             m->nnzb, m->nnzb * bb, int32_t(e0[k]), int32_t(bt->brow[k])});
+      (pass ? anyL : anyA) = true;
+    }
+  }
+  lspcg_solver* s = bt->s;
+  LSPCG_HIP(hipSetDevice(bt->ctx->device));
+  hipStream_t cst = bt->ctx->stream;
+  const int nmat = int(tab.size());
+  if (!bt->utab) {
+    LSPCG_HIP(hipMalloc(&bt->utab, sizeof(CatSlice) * 2 * size_t(ns)));
+    LSPCG_HIP(hipEventCreate(&bt->ev_u0));
+    LSPCG_HIP(hipEventCreate(&bt->ev_u1));
+  }
+  LSPCG_HIP(hipEventRecord(bt->ev_u0, cst));
+  // one launch of <= ~2048 workgroups over all given matrices (gridDim.y of them, the rest strided)
+  int64_t most = 1;
+  for (const CatSlice& d : tab) most = std::max<int64_t>(most, d.nb + 1 + std::max(d.nnzb, d.nval));
+  const unsigned gy = unsigned(std::min(std::max(nmat, 1), 2048));
+  const unsigned gx = unsigned(std::max<int64_t>(1, std::min<int64_t>((most + kThreads - 1) / kThreads, 2048 / gy)));
+  if (nmat) {
+    // the pattern check: every given matrix against its slice in one launch, one flag read.  Before it
+    // has passed nothing is written, so a refused window leaves every system and every L as it was
+    LSPCG_HIP(hipMemcpyAsync(bt->utab, tab.data(), sizeof(CatSlice) * nmat, hipMemcpyHostToDevice, cst));
+    LSPCG_HIP(hipMemsetAsync(s->flag, 0, sizeof(int), cst));
+    launch(k_cat_same_pattern, dim3(gx, gy), dim3(kThreads), cst, nmat, bt->utab, s->flag);
+    LSPCG_HIP(hipGetLastError());
+    int differs = 0;
+    LSPCG_HIP(hipMemcpyAsync(&differs, s->flag, sizeof(int), hipMemcpyDeviceToHost, cst));
+    LSPCG_HIP(hipStreamSynchronize(cst));
+    LSPCG_CHECK(!differs, LSPCG_ERR_FORMAT,
+                "batch_update: a given matrix has another pattern than the system it replaces (nothing written)");
+  }
+  LSPCG_HIP(hipStreamSynchronize(s->stream));  // a running solve reads everything rewritten below
+  const GraphKey key_before = graph_key(s);
+  // From here values are written and views may move: a failure drops the graphs, which hold the old
+  // addresses by value, solves return its code, and the update that follows it reports none kept
+  const bool after_failure = bt->update_failed;
+  bt->update_failed = true;
+  auto steps = [&]() -> int {
+    if (nmat) {
+      by_dtype(bt->dtype, [&](auto t) {
+        launch(k_cat_copy_values<decltype(t)>, dim3(gx, gy), dim3(kThreads), cst, nmat, bt->utab);
+        return 0;
+      });
+      LSPCG_HIP(hipGetLastError());
+    }
+    if (anyA)
+      if (int rc = lspcg_solver_update_matrix(s, nullptr, nullptr)) return rc;
+    const bool new_spai = spai && (anyL || epsilon != s->eps);
+    if (new_spai) {  // Lcat is the installed handle and its pattern has just been checked
+      s->same_L_pattern = true;
+      const int rc = lspcg_solver_set_spai(s, bt->Lcat, epsilon, nullptr);
+      s->same_L_pattern = false;
+      if (rc) return rc;
+    }
+    if (needs_d && (anyA || new_spai))  // both recompute d = diag(A), 0 on padding rows
+      if (int rc = pad_d(bt)) return rc;
+    float ms = 0.f;
+    LSPCG_HIP(hipEventRecord(bt->ev_u1, cst));
+    LSPCG_HIP(hipEventSynchronize(bt->ev_u1));
+    LSPCG_HIP(hipEventElapsedTime(&ms, bt->ev_u0, bt->ev_u1));
+    if (t_ms) *t_ms = ms;
+    return LSPCG_OK;
+  };
+  if (int rc = steps()) {
+    bt->graphs.clear();
+    bt->update_rc = rc;
+    return rc;
+  }
+  bt->update_failed = false;
+  bt->update_rc = LSPCG_OK;
+  const bool kept = !after_failure && graph_key(s) == key_before;
+  if (!kept) bt->graphs.clear();
+  if (graphs_kept) *graphs_kept = kept ? 1 : 0;
   return LSPCG_OK;
 }
 
@@ -755,6 +927,10 @@ int lspcg_batch_solve_coef(lspcg_batch* bt, const void* const* b, void* const* x
   LSPCG_CHECK(bt && b && x && iters && status, LSPCG_ERR_ARG, "batch_solve: NULL argument");
   const int ns = bt->nsys;
   for (int k = 0; k < ns; ++k) LSPCG_CHECK(b[k] && x[k], LSPCG_ERR_ARG, "batch_solve: NULL vector " + std::to_string(k));
+  if (bt->update_failed) {
+    set_error("batch_solve: the last lspcg_batch_update failed and left views that may have moved; update again first");
+    return bt->update_rc;
+  }
   lspcg_solver* s = bt->s;
   LSPCG_HIP(hipSetDevice(bt->ctx->device));
   hipStream_t st = s->stream;

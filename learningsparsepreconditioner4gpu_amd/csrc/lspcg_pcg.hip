@@ -87,8 +87,12 @@ static int build_sell(lspcg_solver* s, int w, const lspcg_mat* view) {
   // its address -- and with it every captured iteration graph -- stays valid (graph_key)
   // (the pattern may have been rebuilt at the same host address -- set_dot_order's switch back to the
   // unpermuted A -- so the array's entry count must match the pattern's, not just the pointers)
-  if (w > 0 && s->use_sell && s->sv[w] && s->sp[w] && s->sp[w] == s->sp[0] &&
-      view->rowptr == s->Av.rowptr && view->colind == s->Av.colind && view->storage_dtype() == s->svd[w] &&
+  // The same holds for a pattern of L's / Lᵀ's own when the caller vouches for it (same_L_pattern: the
+  // installed handle with new values only, lspcg_batch_update): refilled, not rebuilt.
+  const bool on_A = s->sp[w] && s->sp[w] == s->sp[0] && view->rowptr == s->Av.rowptr && view->colind == s->Av.colind;
+  const bool on_own = s->same_L_pattern && s->sp[w] == &s->spat[w] &&
+                      !(s->sp[0] && view->rowptr == s->Av.rowptr && view->colind == s->Av.colind);
+  if (w > 0 && s->use_sell && s->sv[w] && s->sp[w] && (on_A || on_own) && view->storage_dtype() == s->svd[w] &&
       s->svn[w] == s->sp[w]->slots()) {
     const SellPattern* P = s->sp[w];
     const int vd = view->storage_dtype();
@@ -514,22 +518,9 @@ int lspcg::solver_create(lspcg_ctx* ctx, const lspcg_mat* A, int precond, bool d
   return LSPCG_OK;
 }
 
-extern "C" {
+namespace lspcg {
 
-int lspcg_solver_create(lspcg_ctx* ctx, const lspcg_mat* A, int precond, lspcg_solver** out) {
-  return solver_create(ctx, A, precond, true, true, out);
-}
-
-// Everything a captured iteration graph holds by value besides the solver's own fixed buffers: the
-// views' arrays (SELL copies or CSR views), their value types, the reduction geometry and ε.  A
-// new L whose views land at the same addresses keeps the graphs (build_sell / make_view refill in
-// place), so a sample-by-sample loop does not re-capture every chunk size per sample.
-struct GraphKey {
-  std::vector<int64_t> v;  // pointers, kinds and sizes, in a fixed order
-  double eps = 0.0;
-  bool operator==(const GraphKey& o) const { return v == o.v && eps == o.eps; }
-};
-static GraphKey graph_key(const lspcg_solver* s) {
+GraphKey graph_key(const lspcg_solver* s) {
   GraphKey k;
   auto put = [&](auto x) {
     if constexpr (std::is_pointer<decltype(x)>::value) k.v.push_back(int64_t(reinterpret_cast<intptr_t>(x)));
@@ -567,6 +558,14 @@ static GraphKey graph_key(const lspcg_solver* s) {
   }
   k.eps = s->eps;
   return k;
+}
+
+}  // namespace lspcg
+
+extern "C" {
+
+int lspcg_solver_create(lspcg_ctx* ctx, const lspcg_mat* A, int precond, lspcg_solver** out) {
+  return solver_create(ctx, A, precond, true, true, out);
 }
 
 int lspcg_solver_set_spai(lspcg_solver* s, const lspcg_mat* L, double epsilon, double* t_prec_ms) {

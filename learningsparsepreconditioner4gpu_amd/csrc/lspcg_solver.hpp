@@ -144,6 +144,8 @@ struct lspcg_solver {
   bool small_sell = true;  // k_pcg_small reads the SELL copies (LSPCG_SMALL_SELL=0: the CSR views)
   bool split_ok = false;   // set_spai found SELL views for the split schedule
   bool dia_ok = true;      // SELL-DIA views allowed (a batch of one-workgroup solves turns them off)
+  bool same_L_pattern = false;  // set around lspcg_solver_set_spai by a caller whose L is the installed handle with
+                                // new values only (lspcg_batch_update): L's and Lᵀ's own SELL patterns are kept
   int dot_order = LSPCG_DOT_COMPENSATED;  // lspcg_solver_set_dot_order
   int dot_threads = 1;
   double* ob_part = nullptr;  // [3 dots x kObMaxThreads chunks] parity-mode chunk totals (k_dot_openblas_item)
@@ -160,6 +162,18 @@ void multi_destroy(lspcg_solver* s);
 // lspcg_solver_create with the batch's switches: no SELL-DIA views (a window of one-workgroup
 // solves), no reordering (lspcg_pcg.hip)
 int solver_create(lspcg_ctx* ctx, const lspcg_mat* A, int precond, bool dia_ok, bool reorder_ok, lspcg_solver** out);
+
+// Everything a captured iteration graph holds by value besides the solver's own fixed buffers: the
+// views' arrays (SELL copies or CSR views), their value types, the reduction geometry and ε.  A
+// new L whose views land at the same addresses keeps the graphs (build_sell / make_view refill in
+// place), so a sample-by-sample loop does not re-capture every chunk size per sample.  The batch's
+// graphs (lspcg_batch.hip) are captured on the same views and follow the same key.
+struct GraphKey {
+  std::vector<int64_t> v;  // pointers, kinds and sizes, in a fixed order
+  double eps = 0.0;
+  bool operator==(const GraphKey& o) const { return v == o.v && eps == o.eps; }
+};
+GraphKey graph_key(const lspcg_solver* s);  // lspcg_pcg.hip
 
 // SpMV of iteration view w with the fused prologue / gather / epilogue, SELL when available.
 template <typename T, class Gx, class Pro, class Epi>

@@ -187,7 +187,7 @@ def _rhs(rhs: str, i: int, s: GraphSample, rhs_vectors: Optional[Dict[int, np.nd
 def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: float = 1e-6, repeat: int = 1,
         rhs: str = "mask", warmup: int = 20, concurrency: int = 1, batch: int = 1, dot_order: str = "compensated",
         dot_threads: int = 1, rhs_vectors: Optional[Dict[int, np.ndarray]] = None, reuse_solver: bool = False,
-        solutions: Optional[Dict[int, torch.Tensor]] = None) -> List[SolveRecord]:
+        solutions: Optional[Dict[int, torch.Tensor]] = None, reuse_batch: bool = False) -> List[SolveRecord]:
     """The ``Neural+CUDA`` row of infer.py:278-331 (GNN -> L, A; ext_spai PCG).  ``concurrency``
     > 1 keeps that many solves of this rank in flight at once (run_sharded_concurrent): the same
     iterates and counts, a higher batch throughput on the reference's mid-size systems.  ``batch``
@@ -203,7 +203,14 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
     solver's matrix (``system_matrix(out=)``) and installed with ``update_matrix``, its L with the
     in-place ``set_spai`` -- instead of the reference's one solver per repeat; a sample whose pattern
     differs (``ERR_FORMAT``) gets a fresh solver, which is kept in turn.  The same counts and iterates.
+    ``reuse_batch`` (opt-in; fixed-topology datasets, ``batch`` > 1): one lockstep batch per window
+    shape is kept across windows and takes each window's A and L in place
+    (``BatchedConjugateGradient.update``: the block-diagonal patterns, views, tile maps and graphs are
+    kept); a window of another pattern gets a fresh batch, which is kept in turn.  The same counts and
+    iterates.
     ``solutions`` (optional dict): receives sample i's last iterate under key i."""
+    if reuse_batch and batch <= 1:
+        raise ValueError("reuse_batch keeps a lockstep batch across windows: it needs batch > 1")
     if batch > 1 and dot_order != "compensated":
         raise ValueError("batch > 1 runs the compensated dot order only; use batch=1 for dot_order='openblas'")
     if reuse_solver and (batch > 1 or concurrency > 1):
@@ -291,10 +298,15 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
         return SolveRecord(index=i, iters=it, rel_res=info["rel_res"], t_prec=prec, t_solve=sol, n=A.n, nnz=A.nnz,
                            converged=info["converged"])
 
+    kept_batches = {} if reuse_batch else None  # validate._batch_generic's `reuse`
+
     def finish_batch(jobs) -> List[SolveRecord]:
         infos = [{} for _ in jobs]
         out = pcg_batch([j[1] for j in jobs], [j[3] for j in jobs], [j[2] for j in jobs], ws.epsilon,
-                        rtol=rtol, infos=infos, repeat=repeat)
+                        rtol=rtol, infos=infos, repeat=repeat, reuse=kept_batches)
+        if solutions is not None:
+            for j, info in zip(jobs, infos):
+                solutions[j[0]] = info["x"]
         return [SolveRecord(index=j[0], iters=it, rel_res=info["rel_res"], t_prec=j[4], t_solve=sol, n=j[1].n,
                             nnz=j[1].nnz, converged=info["converged"]) for j, (it, _, sol), info in zip(jobs, out, infos)]
 
@@ -328,15 +340,19 @@ def run(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, rtol: floa
 def run_baseline(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, method: str, rtol: float = 1e-6,
                  repeat: int = 1, rhs: str = "mask", dot_order: str = "compensated",
                  dot_threads: int = 1, rhs_vectors: Optional[Dict[int, np.ndarray]] = None,
-                 batch: int = 1) -> List[SolveRecord]:
+                 batch: int = 1, reuse_batch: bool = False) -> List[SolveRecord]:
     """The ``PCG-{method}-cuda`` rows (infer.py:310-321: get_cg_iter_time with method none /
     diagonal / ainv / ic on the same A and rhs).  A non-converged solve raises RuntimeError in
     the reference (caught at :363); here its row is NaN and left out of the statistics.
     ``batch`` > 1 solves this rank's systems in lockstep windows of that many for none / diagonal /
     ainv (run_sharded_batched, validate.get_cg_iter_time_batch: the same counts and iterates, a
     record's t_prec / t_solve its shares of the window's); ``ic`` has no lockstep form and stays one
-    solve at a time, as does the parity dot order."""
+    solve at a time, as does the parity dot order.  ``reuse_batch``: as ``run``'s, for the rows that
+    run in windows."""
+    if reuse_batch and batch <= 1:
+        raise ValueError("reuse_batch keeps a lockstep batch across windows: it needs batch > 1")
     dev = torch.device("cuda", torch.cuda.current_device())
+    kept_batches = {} if reuse_batch else None
 
     def nan_row(i, A) -> SolveRecord:
         return SolveRecord(index=i, iters=float("nan"), rel_res=float("nan"), t_prec=float("nan"),
@@ -349,7 +365,7 @@ def run_baseline(samples: Sequence[GraphSample], ws: SimpleInferenceWorkspace, m
     def finish_batch(jobs) -> List[SolveRecord]:
         infos, errors = [{} for _ in jobs], [None for _ in jobs]
         out = get_cg_iter_time_batch([j[1] for j in jobs], [j[2] for j in jobs], method, rtol=rtol, infos=infos,
-                                     repeat=repeat, errors=errors)
+                                     repeat=repeat, errors=errors, reuse=kept_batches)
         return [nan_row(i, A) if o is None else
                 SolveRecord(index=i, iters=o[0], rel_res=info["rel_res"], t_prec=o[1], t_solve=o[2], n=A.n, nnz=A.nnz,
                             converged=info["converged"]) for (i, A, _), o, info in zip(jobs, out, infos)]
@@ -470,6 +486,9 @@ def main(argv=None):
     ap.add_argument("--reuse-solver", action="store_true",
                     help="with --fixed-topology: keep one solver per sample shape for the Neural row and install each "
                          "sample's A and L on it in place (update_matrix) instead of one solver per repeat")
+    ap.add_argument("--reuse-batch", action="store_true",
+                    help="with --fixed-topology and --batch > 1: keep one lockstep batch per window shape and install "
+                         "each window's A and L on it in place instead of one batch per window")
     ap.add_argument("--baselines", default="none,diagonal,ainv,ic",
                     help="comma list of PCG-{method}-cuda rows (infer.py:310-321); '' for none")
     ap.add_argument("--dot-order", default="compensated", choices=["compensated", "openblas"],
@@ -489,6 +508,8 @@ def main(argv=None):
 
     if args.reuse_solver and not (args.folder and args.fixed_topology):
         ap.error("--reuse-solver needs --folder with --fixed-topology (samples that share one pattern)")
+    if args.reuse_batch and args.batch <= 1:
+        ap.error("--reuse-batch needs --batch > 1 (it keeps a lockstep batch across windows)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # one GPU per local rank; more ranks than GPUs (a gloo rehearsal on one GPU) share them
@@ -521,11 +542,12 @@ def main(argv=None):
     # its one-at-a-time sum in wall time (profiles/batch_kinds_probe.json); ic has none
     for m in [b for b in args.baselines.split(",") if b]:
         rows[f"PCG-{m}-cuda"] = run_baseline(samples, ws, m, rtol=args.rtol, repeat=args.repeat, rhs=args.rhs,
-                                             rhs_vectors=rhs_vectors, batch=args.batch, **dots)
+                                             rhs_vectors=rhs_vectors, batch=args.batch,
+                                             reuse_batch=args.reuse_batch, **dots)
     key = "Neural+HIP" if args.hip_key else "Neural+CUDA"
     rows[key] = run(samples, ws, rtol=args.rtol, repeat=args.repeat, rhs=args.rhs, warmup=args.warmup,
                     concurrency=args.concurrency, batch=args.batch, rhs_vectors=rhs_vectors,
-                    reuse_solver=args.reuse_solver, **dots)
+                    reuse_solver=args.reuse_solver, reuse_batch=args.reuse_batch, **dots)
     recs = rows[key]
     if args.cpu_rows and (not dist.is_initialized() or dist.get_rank() == 0):
         rows.update(run_cpu_rows(samples, ws, rtol=args.rtol, repeat=args.repeat, rhs=args.rhs,

@@ -67,6 +67,30 @@ def _as_device_matrix(M, dtype, block_size: int, ctx: Context) -> DeviceMatrix:
     return DeviceMatrix.from_scipy(sp.csr_matrix(M), dtype=dtype, block_size=block_size, ctx=ctx)
 
 
+def _sorted_host_matrix(M, dtype, bs: int, name: str):
+    """The scipy matrix ``M`` of ``dtype`` as sorted CSR (``bs`` 1) or sorted BSR with ``bs`` x ``bs``
+    blocks, the arrays a ``DeviceMatrix`` of that block size stores; the caller's matrix keeps its
+    order.  Another dtype, or no scipy matrix: ``TypeError``."""
+    if not sp.issparse(M):
+        raise TypeError(f"{name} must be a scipy sparse matrix or a DeviceMatrix, got {type(M).__name__}")
+    if np.dtype(M.dtype) != dtype:
+        raise TypeError(f"matrix dtype {M.dtype} differs from solver dtype {dtype}")
+    if bs == 1:
+        out = sp.csr_matrix(M)
+        if not out.has_sorted_indices:
+            out = out.sorted_indices()
+        return out
+    if isinstance(M, sp.bsr_matrix) and M.blocksize == (bs, bs):
+        out = M
+        if not out.has_sorted_indices:  # sort a copy: the caller's matrix keeps its order
+            out = out.copy()
+            out.sort_indices()
+        return out
+    out = sp.bsr_matrix(sp.csr_matrix(M), blocksize=(bs, bs))
+    out.sort_indices()
+    return out
+
+
 def _copy_values(dst: DeviceMatrix, src: DeviceMatrix) -> None:
     """``dst.set_values`` from ``src`` on the device, ``src``'s pattern checked against ``dst``'s."""
     dev = dst.ctx.torch_device
@@ -179,24 +203,7 @@ class PreconditionedConjugateGradient:
                                                            "or block size (nothing written)")
                 _copy_values(self.A, A_new)
             else:
-                if not sp.issparse(A_new):
-                    raise TypeError(f"A_new must be a scipy sparse matrix or a DeviceMatrix, got {type(A_new).__name__}")
-                if np.dtype(A_new.dtype) != self.dtype:
-                    raise TypeError(f"matrix dtype {A_new.dtype} differs from solver dtype {self.dtype}")
-                bs = self.A.block_size
-                if bs == 1:
-                    M = sp.csr_matrix(A_new)
-                    if not M.has_sorted_indices:
-                        M = M.sorted_indices()
-                else:
-                    if isinstance(A_new, sp.bsr_matrix) and A_new.blocksize == (bs, bs):
-                        M = A_new
-                        if not M.has_sorted_indices:  # sort a copy: the caller's matrix keeps its order
-                            M = M.copy()
-                            M.sort_indices()
-                    else:
-                        M = sp.bsr_matrix(sp.csr_matrix(A_new), blocksize=(bs, bs))
-                        M.sort_indices()
+                M = _sorted_host_matrix(A_new, self.dtype, self.A.block_size, "A_new")
                 if M.shape != self.A.shape or M.indices.size != self.A.nnzb:
                     raise _lib.LspcgError(_lib.ERR_FORMAT, "update_matrix: the new matrix has another size or entry "
                                                            "count (nothing written)")
@@ -513,6 +520,86 @@ class BatchedConjugateGradient:
         if h is not None and h.value and _lib._lib is not None:
             _lib._lib.lspcg_batch_destroy(h)
             self.handle = None
+
+    def update(self, As=None, Ls=None, epsilon: Optional[float] = None) -> Tuple[float, bool]:
+        """New values of A and / or L on this batch, same patterns (``lspcg_batch_update``): returns
+        ``(setup_time_s, graphs_kept)``.  ``As`` / ``Ls``: lists of ``len(self)`` entries, each a scipy
+        matrix, a ``DeviceMatrix`` or ``None`` (that system's matrix stays); ``epsilon=None`` keeps ε.
+        Only what depends on values is redone: the block-diagonal copies, their SELL
+        patterns, the tile maps and -- unless the values' fp32-exactness or ε changed -- the captured
+        graphs are kept, and the next solves give the bits of a batch created on the resulting matrices.
+        Checked before any native call: a wrong list length, ``Ls`` for a kind that takes none, or
+        nothing to update raise ``ValueError``; another dtype ``TypeError``; another size, entry count or
+        block size ``LspcgError`` (``ERR_FORMAT``).  Another pattern with the same counts is found on
+        the device and raises ``ERR_FORMAT`` as well; in every such case nothing was written and the
+        batch still solves its old systems.  ``"ainv"``: the factors of the given ``As`` are recomputed
+        first (``ainv0()``), so a breakdown raises ``LspcgError`` (``ERR_BREAKDOWN``) with the batch
+        untouched."""
+        k = len(self.n)
+        needs_L = self.preconditioner in ("ext_spai", "ext_spai_scaled")
+        if Ls is not None and not needs_L:
+            raise ValueError(f"preconditioner {self.preconditioner!r} takes no Ls")
+        if not needs_L:
+            epsilon = None  # none / diagonal have no ε, ainv runs with ε = 0
+        As = None if As is None else list(As)
+        Ls = None if Ls is None else list(Ls)
+        for name, Ms in (("As", As), ("Ls", Ls)):
+            if Ms is not None and len(Ms) != k:
+                raise ValueError(f"{name}: {len(Ms)} entries for {k} systems")
+        if not any(M is not None for Ms in (As, Ls) if Ms is not None for M in Ms) and \
+                (epsilon is None or float(epsilon) == self.epsilon):
+            raise ValueError("update: nothing to update (no matrix given and the same epsilon)")
+
+        def host_checked(Ms, have, name):
+            out = []
+            for j, M in enumerate(Ms or ()):
+                if M is None or isinstance(M, DeviceMatrix):
+                    if M is not None:
+                        if M.dtype_code != lspcg_dtype(self.dtype):
+                            raise TypeError(f"{name}[{j}]: matrix dtype {M.dtype} differs from batch dtype {self.dtype}")
+                        if (M.n, M.nnzb, M.block_size) != (have[j].n, have[j].nnzb, have[j].block_size):
+                            raise _lib.LspcgError(_lib.ERR_FORMAT, f"update: {name}[{j}] has another size, entry count "
+                                                                   "or block size (nothing written)")
+                    out.append(M)
+                    continue
+                H = _sorted_host_matrix(M, self.dtype, have[j].block_size, f"{name}[{j}]")
+                if H.shape != (have[j].n, have[j].n) or H.indices.size != have[j].nnzb:
+                    raise _lib.LspcgError(_lib.ERR_FORMAT, f"update: {name}[{j}] has another size or entry count "
+                                                           "(nothing written)")
+                out.append(H)
+            return out
+
+        As, Ls = host_checked(As, self.A, "As"), host_checked(Ls, self.L, "Ls")  # ([] = not given)
+
+        def on_device(Ms, have):
+            return [M if M is None or isinstance(M, DeviceMatrix) else
+                    DeviceMatrix.from_scipy(M, dtype=self.dtype, block_size=have[j].block_size, ctx=self.ctx)
+                    for j, M in enumerate(Ms)]
+
+        As, Ls = on_device(As, self.A), on_device(Ls, self.L)
+        t_fac = 0.0
+        eps = self.epsilon if epsilon is None else float(epsilon)
+        if self.preconditioner == "ainv" and As:
+            # before the native call, as at creation: a breakdown leaves the batch as it was
+            fac = [None if M is None else M.ainv0() for M in As]
+            Ls = [None if f is None else f[0] for f in fac]
+            t_fac = float(sum(f[1] for f in fac if f is not None))
+            eps = 0.0
+
+        def handles(Ms):
+            return (C.c_void_p * k)(*[None if M is None else M.handle.value for M in Ms]) if Ms else None
+
+        ms, kept = C.c_double(), C.c_int()
+        _lib.call("lspcg_batch_update", self.handle, handles(As), handles(Ls), eps, C.byref(ms), C.byref(kept))
+        for Ms, have in ((As, self.A), (Ls, self.L)):
+            for j, M in enumerate(Ms):
+                if M is not None:
+                    have[j] = M
+        self.epsilon = eps
+        t = ms.value / 1e3 + t_fac
+        if self.preconditioner == "ainv":
+            self.setup_time = t
+        return t, bool(kept.value)
 
     def __len__(self):
         return len(self.n)

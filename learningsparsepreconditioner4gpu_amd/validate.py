@@ -199,7 +199,8 @@ def get_pcg_iter_time(A, gt, spai, epsilon: float, rtol=1e-6, max_iter=0, repeat
                         dot_order, dot_threads)
 
 
-def _batch_generic(kind, As, gts, spais, epsilon, rtol, max_iter, dtype, infos, repeat, single, errors=None):
+def _batch_generic(kind, As, gts, spais, epsilon, rtol, max_iter, dtype, infos, repeat, single, errors=None,
+                   reuse=None):
     """A window of independent systems as ONE lockstep batch of preconditioner ``kind``
     (linalg.BatchedConjugateGradient).  Per system ``(iters, prec_s, solve_s)``: the batch's setup
     (block-diagonal copy, Lᵀ / AINV factors and views: host wall) and device solve time split evenly
@@ -208,7 +209,11 @@ def _batch_generic(kind, As, gts, spais, epsilon, rtol, max_iter, dtype, infos, 
     system at a time instead, on the GPU, by ``single(j, A, L, info)`` -- every system then gets
     what the sequential path gives it.  ``errors`` (a list, one slot per system): the three baseline kinds'
     "CG did not converge" of get_cg_iter_time per system -- system j's entry is then None and
-    ``errors[j]`` the RuntimeError; without the list the first such error is raised."""
+    ``errors[j]`` the RuntimeError; without the list the first such error is raised.  ``reuse`` (a dict
+    the caller keeps across windows): the batch is kept under its kind and the tuple of per-system
+    ``(n, nnzb, block_size)``, and a later window with that key is installed on it with
+    ``BatchedConjugateGradient.update`` (same patterns: only what depends on values is redone); another
+    pattern (``ERR_FORMAT``, nothing written) gets a fresh batch, which replaces the kept one."""
     Ads = [_prepare(A, dtype) for A in As]
     Lds = None if spais is None else [L if isinstance(L, DeviceMatrix) else _prepare(L, dtype) for L in spais]
     bs = [_device_rhs(A, gt) for A, gt in zip(Ads, gts)]
@@ -221,13 +226,32 @@ def _batch_generic(kind, As, gts, spais, epsilon, rtol, max_iter, dtype, infos, 
         errors[j] = e
         return None
 
-    try:
-        t0 = time.perf_counter()
-        B = BatchedConjugateGradient(Ads, Lds, epsilon, dtype=dtype, preconditioner=kind)
-        prec = time.perf_counter() - t0
-    except _lib.LspcgError as e:
-        if e.code not in (_lib.ERR_UNSUPPORTED, _lib.ERR_BREAKDOWN):
-            raise
+    B, one_by_one = None, False
+    key = (kind, tuple((A.n, A.nnzb, A.block_size) for A in Ads))
+    cand = reuse.get(key) if reuse is not None else None
+    if cand is not None and cand.dtype == np.dtype(dtype):
+        try:  # the kept batch of this shape takes the window's values in place
+            t0 = time.perf_counter()
+            cand.update(Ads, Lds, epsilon if Lds is not None else None)
+            prec = time.perf_counter() - t0
+            B = cand
+        except _lib.LspcgError as e:
+            if e.code == _lib.ERR_BREAKDOWN:  # AINV(0) of a new A: as at creation
+                one_by_one = True
+            elif e.code != _lib.ERR_FORMAT:  # another pattern: nothing was written; a fresh batch replaces it
+                raise
+    if B is None and not one_by_one:
+        try:
+            t0 = time.perf_counter()
+            B = BatchedConjugateGradient(Ads, Lds, epsilon, dtype=dtype, preconditioner=kind)
+            prec = time.perf_counter() - t0
+            if reuse is not None:
+                reuse[key] = B
+        except _lib.LspcgError as e:
+            if e.code not in (_lib.ERR_UNSUPPORTED, _lib.ERR_BREAKDOWN):
+                raise
+            one_by_one = True
+    if one_by_one:
         out = []
         for j in range(k):
             info = {} if infos is not None else None
@@ -259,30 +283,34 @@ def _batch_generic(kind, As, gts, spais, epsilon, rtol, max_iter, dtype, infos, 
 
 
 def get_pcg_iter_time_batch(As, gts, spais, epsilon: float, rtol=1e-6, max_iter=0, dtype=np.float64,
-                            infos: Optional[list] = None, repeat: int = 1) -> List[Tuple[float, float, float]]:
+                            infos: Optional[list] = None, repeat: int = 1,
+                            reuse: Optional[dict] = None) -> List[Tuple[float, float, float]]:
     """get_pcg_iter_time over a window of independent systems solved as ONE lockstep batch
     (linalg.BatchedConjugateGradient; the reference calls get_pcg_iter_time once per sample,
     infer.py:322).  Per system ``(iters, prec_s, solve_s)``: the batch's setup (block-diagonal
     copy, Lᵀ and views: host wall) and device solve time split evenly over its systems, the solve
     averaged over ``repeat`` solves from x0 = 0 like get_pcg_iter_time (validate.py:111-121).  A
-    window without a SELL view (irregular rows) is solved one system at a time instead, on the GPU."""
+    window without a SELL view (irregular rows) is solved one system at a time instead, on the GPU.
+    ``reuse`` (optional dict kept by the caller across windows): windows of equal patterns share one
+    batch, each installed on it in place (``BatchedConjugateGradient.update``); the same results."""
     return _batch_generic("ext_spai", As, gts, spais, epsilon, rtol, max_iter, dtype, infos, repeat,
                           lambda j, A, L, info: get_pcg_iter_time(A, gts[j], L, epsilon, rtol, max_iter, repeat, dtype,
-                                                                  device="cuda", info=info))
+                                                                  device="cuda", info=info), reuse=reuse)
 
 
 def get_pcg_scaled_iter_time_batch(As, gts, spais, epsilon: float, rtol=1e-6, max_iter=0, dtype=np.float64,
-                                   infos: Optional[list] = None, repeat: int = 1) -> List[Tuple[float, float, float]]:
+                                   infos: Optional[list] = None, repeat: int = 1,
+                                   reuse: Optional[dict] = None) -> List[Tuple[float, float, float]]:
     """get_pcg_scaled_iter_time over a window solved as one lockstep batch: the twin of
     get_pcg_iter_time_batch for ext_spai_scaled (the same return shape and fall-back)."""
     return _batch_generic("ext_spai_scaled", As, gts, spais, epsilon, rtol, max_iter, dtype, infos, repeat,
                           lambda j, A, L, info: get_pcg_scaled_iter_time(A, gts[j], L, epsilon, rtol, max_iter, repeat,
-                                                                         dtype, device="cuda", info=info))
+                                                                         dtype, device="cuda", info=info), reuse=reuse)
 
 
 def get_cg_iter_time_batch(As, gts, method: str, rtol=1e-6, max_iter=0, dtype=np.float64,
-                           infos: Optional[list] = None, repeat: int = 1,
-                           errors: Optional[list] = None) -> List[Optional[Tuple[float, float, float]]]:
+                           infos: Optional[list] = None, repeat: int = 1, errors: Optional[list] = None,
+                           reuse: Optional[dict] = None) -> List[Optional[Tuple[float, float, float]]]:
     """get_cg_iter_time (method none / diagonal / ainv) over a window solved as one lockstep batch;
     the return shape and the fall-back of get_pcg_iter_time_batch.  A system that reaches max_iter
     raises ``RuntimeError("CG did not converge")`` as get_cg_iter_time does; with ``errors`` (a list
@@ -293,7 +321,7 @@ def get_cg_iter_time_batch(As, gts, method: str, rtol=1e-6, max_iter=0, dtype=np
     return _batch_generic(method, As, gts, None, 0.0, rtol, max_iter, dtype, infos, repeat,
                           lambda j, A, L, info: get_cg_iter_time(A, gts[j], rtol, max_iter, dtype, repeat,
                                                                  device="cuda", method=method, info=info),
-                          errors=errors)
+                          errors=errors, reuse=reuse)
 
 
 def get_pcg_scaled_iter_time(A, gt, spai, epsilon: float, rtol=1e-6, max_iter=0, repeat=1, dtype=np.float64,
