@@ -116,6 +116,53 @@ int lspcg_mat_scale_columns(lspcg_mat* A, const void* d);
 int lspcg_mat_rcm(const lspcg_mat* A, int32_t* perm, int* applied, double* mean_offset_before,
                   double* mean_offset_after);
 
+/* ---- the GNN's input sample of a matrix on the device (neural_cg/data.py:218-336 make_data) ----
+ * A: scalar CSR or BSR 3x3, fp32 or fp64, rows sorted (what lspcg_mat_diagonal requires).  Below
+ * E = nnzb, b = block size, nb = block rows, v = a stored value widened to double. */
+#define LSPCG_NORM_NONE 0
+#define LSPCG_NORM_MEAN 1
+#define LSPCG_NORM_FROB 2
+#define LSPCG_NORM_L1 3
+#define LSPCG_REDUCE_DISABLE 0
+#define LSPCG_REDUCE_SUM 1
+#define LSPCG_REDUCE_MEAN 2
+#define LSPCG_REDUCE_MAX 3
+#define LSPCG_REDUCE_MIN 4
+typedef struct lspcg_sample_desc {
+  int normalize;             /* LSPCG_NORM_*   (make_data's normalize_matrix) */
+  int mask_as_node_feature;  /* 0 / 1 */
+  int edge_reduce;           /* LSPCG_REDUCE_* (use_edge_features_as_node_feature) */
+  int node_in;               /* columns of node_features (0: none) */
+} lspcg_sample_desc;
+
+/* edge_index (device int64 [2][nnzb]) <- the block COO of A in stored (row-major) order */
+int lspcg_mat_edge_index(const lspcg_mat* A, int64_t* edge_index);
+
+/* make_data of A's block graph; every pointer is a device pointer, the work is issued on ctx's
+ * stream and nothing synchronises except an allocation on first use.
+ *   scale (one DEVICE double, read from there by the later passes): none 1; mean
+ *     1 / (sum|v| / double(E b b)); frob 1 / sqrt(sum v^2), both sums compensated in a fixed order
+ *     (chunks of 4096 values, then one workgroup) that depends on neither grid nor device, without
+ *     floating-point atomics: the same bits on every call; l1 (b = 1 only, LSPCG_ERR_UNSUPPORTED for
+ *     b = 3) 1 / (max_i sum_j |v_ij| + 1e-7), each row a sequential sum in stored order (scipy's).
+ *   edge_attr[e][b*a+c] = float(scale * v) (also the sample's matrix_values);
+ *   diagonal = float(A_ii * scale) (0 where no diagonal is stored), inv_diag = float(1 / (A_ii *
+ *     scale + 1e-7)), rsqrt_diag = float(1 / sqrt(A_ii * scale + 1e-7)): [nb*b] each, given together
+ *     or all NULL; every value computed in double and rounded once.
+ *   x[nb][F_in] = [node_features (node_in columns) | mask (b columns, when the flag is set; NULL
+ *     mask = ones; mask_dtype LSPCG_F32 / LSPCG_F64, [nb*b]) | reduce (b*b columns, when enabled)],
+ *     F_in = node_in + flag*b + (reduce ? b*b : 0).  The reduce is PyG's scatter(edge_attr,
+ *     edge_index[1]): for node j over the edges with block column j in ascending edge order --
+ *     sum: sequential fp32 adds from 0.0f; mean: that sum / max(count, 1) in fp32; max / min over
+ *     those edges; 0 for a node without incoming edges; no atomics.  The edges grouped by
+ *     destination are built at the first reducing call and stay attached to A (the pattern cannot
+ *     change under lspcg_mat_set_values / lspcg_assemble_into).
+ * LSPCG_ERR_ARG before any launch: E = 0 or nb = 0, an unknown code, node_in > 0 with NULL
+ * node_features, F_in = 0. */
+int lspcg_mat_sample(lspcg_ctx* ctx, lspcg_mat* A, const lspcg_sample_desc* desc, const void* mask,
+                     int mask_dtype, const float* node_features, float* x, float* edge_attr,
+                     float* diagonal, float* inv_diag, float* rsqrt_diag, double* scale);
+
 /* ---- kernels ---- */
 /* y = A x (scipy csr_matvec bit pattern: per-row sequential sum in index order).  x and y must not
  * overlap.  After a reordering lspcg_mat_prepare_spmv (lspcg_mat_spmv_reorder_info) the call gathers x

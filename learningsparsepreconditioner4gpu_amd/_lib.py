@@ -38,6 +38,14 @@ class lspcg_optim_desc(C.Structure):
 
 OPT_KIND = {"sgd": 0, "adam": 1, "adamw": 2}
 
+
+class lspcg_sample_desc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("normalize", "mask_as_node_feature", "edge_reduce", "node_in")]
+
+
+NORM = {"none": 0, "mean": 1, "frob": 2, "l1": 3}  # LSPCG_NORM_*
+REDUCE = {"disable": 0, "sum": 1, "mean": 2, "max": 3, "min": 4}  # LSPCG_REDUCE_*
+
 # name -> (restype, argtypes); the list IS the exported ABI (tests check it against include/lspcg.h)
 SIGNATURES = {
     "lspcg_last_error": (C.c_char_p, []),
@@ -56,6 +64,8 @@ SIGNATURES = {
     "lspcg_mat_diagonal": (C.c_int, [vp, vp]),
     "lspcg_mat_rcm": (C.c_int, [vp, vp, C.POINTER(C.c_int), p_f64, p_f64]),
     "lspcg_mat_scale_columns": (C.c_int, [vp, vp]),
+    "lspcg_mat_edge_index": (C.c_int, [vp, vp]),
+    "lspcg_mat_sample": (C.c_int, [vp, vp, C.POINTER(lspcg_sample_desc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "lspcg_spmv": (C.c_int, [vp, vp, vp, vp]),
     "lspcg_spmv_timed": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int64, p_f64]),
     "lspcg_spmv_variant_timed": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int64, p_f64]),

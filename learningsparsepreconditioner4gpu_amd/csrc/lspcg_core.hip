@@ -368,6 +368,7 @@ int lspcg_mat_destroy(lspcg_mat* A) {
   if (!A) return LSPCG_OK;
   (void)hipSetDevice(A->ctx->device);
   drop_sell(A);
+  mat_drop_sample_aux(A);
   (void)hipFree(A->rowptr);
   (void)hipFree(A->colind);
   (void)hipFree(A->vals);

@@ -566,6 +566,10 @@ __device__ __forceinline__ double round_to(double v) {
 
 struct lspcg_mat;
 namespace lspcg {
+// what lspcg_mat_sample keeps on its matrix (lspcg_sample.hip): the edges grouped by destination and
+// the sum's partials; released with the matrix
+struct SampleAux;
+void mat_drop_sample_aux(lspcg_mat* A);
 // (Re)allocate m->colind / m->vals for nnzb stored blocks with zeroed kEntryPad padding.
 int mat_alloc_entries(lspcg_mat* m, int64_t nnzb);
 // New handle with rowptr[nb+1] and padded entry arrays (contents uninitialised).
@@ -637,4 +641,6 @@ struct lspcg_mat {
   int storage_dtype() const { return val_dtype < 0 ? dtype : val_dtype; }
   // optional SELL-64 copy for lspcg_spmv (lspcg_mat_prepare_spmv; lspcg_sell.hpp), owned
   struct SellCopy* sell = nullptr;
+  // optional destination grouping and scratch of lspcg_mat_sample (pattern only: set_values keeps it), owned
+  lspcg::SampleAux* sample_aux = nullptr;
 };

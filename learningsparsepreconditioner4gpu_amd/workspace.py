@@ -320,6 +320,13 @@ class SimpleInferenceWorkspace:
         return self._assemble(s, s.matrix_values, block_output, out=out)
 
 
+    def live_solver(self, A, mask=None, node_features=None, dtype=np.float64, **sample_options) -> "LiveSolver":
+        """The whole chain on a matrix that lives on the device (a simulation's ``DeviceMatrix``, or
+        ``DeviceMatrix.from_device_csr``): its sample built on the device (``data.DeviceSampler``),
+        ``system_matrix``, a solver of this workspace's preconditioner kind, ``inference_step`` and
+        ``set_spai`` -- see :class:`LiveSolver`.  ``sample_options``: ``make_sample``'s keywords."""
+        return LiveSolver(self, A, mask=mask, node_features=node_features, dtype=dtype, **sample_options)
+
     def condition_number(self, sample: GraphSample, kind: str = "neural", **kw):
         """κ(M⁻¹A) of ``sample``'s system under preconditioner ``kind`` -- the reference's ``cond.py``
         columns ``neural, none, diag, ainv, ichol`` -- from one PCG solve's scalars
@@ -342,6 +349,136 @@ class SimpleInferenceWorkspace:
             L, _ = self.inference_step(s)
             solver.set_spai(L, self.epsilon, block_size=L.block_size)
         return spectrum.condition_number(solver, **kw)
+
+
+class LiveSolver:
+    """A matrix on the device -> GNN input -> L -> PCG, with nothing of the matrix on the host.
+
+    Fields: ``sampler`` (``data.DeviceSampler`` of ``A``), ``sample`` (its last ``GraphSample``),
+    ``A_sys`` (``ws.system_matrix(sample)``: the scaled, masked system, as the reference's infer.py
+    assembles it from a sample), ``L`` (the workspace's ``inference_step``) and ``solver``
+    (``PreconditionedConjugateGradient(A_sys, preconditioner=ws.neural_precond)`` with L installed).
+
+    After new values on the same pattern (``A.set_values(...)``, ``assemble(..., out=A)``),
+    :meth:`refresh` runs ``sampler.sample()``, ``system_matrix(sample, out=A_sys)``,
+    ``solver.update_matrix()``, ``inference_step`` and ``set_spai``: the sampler keeps its
+    ``edge_index`` tensor, so the GNN's graph analysis is reused, and the solver keeps its views,
+    ordering and graphs.  :meth:`solve` hands the solver ``matrix_scale * b`` and, where the fp32
+    values of the assembled system leave the residual against the caller's own A above the bound,
+    refines with that A, so x solves ``mask(A) x = b`` for the caller's unscaled A."""
+
+    def __init__(self, ws: "SimpleInferenceWorkspace", A, mask=None, node_features=None, dtype=np.float64,
+                 **sample_options):
+        from .data import DeviceSampler
+        from .linalg import PreconditionedConjugateGradient
+
+        self.ws = ws
+        self.sampler = DeviceSampler(A, mask=mask, node_features=node_features, **sample_options)
+        if self.sampler.block_size != ws.block_size:
+            raise ValueError(f"the matrix has block size {self.sampler.block_size}, the workspace {ws.block_size}")
+        self.sample = self.sampler.sample()
+        self.A_sys = ws.system_matrix(self.sample)
+        self.solver = PreconditionedConjugateGradient(self.A_sys, device="cuda", preconditioner=ws.neural_precond,
+                                                      dtype=dtype, ctx=self.A_sys.ctx)
+        self.L, self.gnn_time = ws.inference_step(self.sample)
+        self.solver.set_spai(self.L, ws.epsilon, block_size=self.L.block_size)
+        self.graphs_kept: Optional[bool] = None  # of the last refresh's update_matrix
+        self.last_solve: Optional[dict] = None   # of the last solve(): refinements, relative_residual, iters
+
+    STEPS = ("sample", "system_matrix", "update_matrix", "inference_step", "set_spai")
+
+    def refresh(self, node_features=None) -> dict:
+        """New values of the sampler's matrix on this solver (see the class).  Returns, per step of
+        ``STEPS`` and for ``"total"``, ``{"wall": s, "device": s}``: the host time spent in the call and
+        the device time between events recorded around it (``total``: until the device has finished)."""
+        ws, dev = self.ws, self.A_sys.ctx.torch_device
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(len(self.STEPS) + 1)]
+        walls = []
+        with torch.cuda.device(dev):
+            torch.cuda.synchronize(dev)
+            t_begin = t0 = time()
+            marks[0].record()
+
+            def done(k):
+                nonlocal t0
+                marks[k].record()
+                t1 = time()
+                walls.append(t1 - t0)
+                t0 = t1
+
+            self.sample = self.sampler.sample(node_features=node_features)
+            done(1)
+            ws.system_matrix(self.sample, out=self.A_sys)
+            done(2)
+            _, self.graphs_kept = self.solver.update_matrix()
+            done(3)
+            self.L, self.gnn_time = ws.inference_step(self.sample)
+            done(4)
+            self.solver.set_spai(self.L, ws.epsilon, block_size=self.L.block_size)
+            done(5)
+            torch.cuda.synchronize(dev)
+            total = time() - t_begin
+        out = {name: {"wall": walls[k], "device": marks[k].elapsed_time(marks[k + 1]) / 1e3}
+               for k, name in enumerate(self.STEPS)}
+        out["total"] = {"wall": total, "device": marks[0].elapsed_time(marks[-1]) / 1e3}
+        return out
+
+    def residual(self, b: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """``b - mask(A) x`` with the caller's own matrix (its values, not the sample's fp32 ones):
+        ``mask(A) = M A M + (I - M)`` for the 0 / 1 mask M, one ``lspcg_spmv`` of the sampler's matrix."""
+        A = self.sampler.A
+        m = self.sampler.mask.reshape(-1).to(x.dtype)
+        y = A.matvec((m * x).to(A.dtype)).to(x.dtype)
+        return b - (m * y + (1.0 - m) * x)
+
+    def solve(self, b: torch.Tensor, x: torch.Tensor, rtol: float = 1e-6, max_iter: int = 0, refine: int = 20, **kw):
+        """x (in: the start, out: the solution) solves ``mask(A) x = b`` for the caller's unscaled A:
+        ``|b - mask(A) x| <= rtol |b|``.
+
+        The first step forwards to ``solver.solve`` with ``matrix_scale * b`` as the right-hand side
+        (the assembled system is the scaled one; at masked unknowns, whose rows are the identity, the
+        right-hand side is ``b`` itself).  That system carries the sample's fp32 ``matrix_values``, as the
+        reference's does, so against A the solution has a residual floor of about 6e-8 times the
+        condition number.  Where the true residual (:meth:`residual`) is above ``rtol |b|`` after the
+        forward, up to ``refine`` steps of iterative refinement follow: the same solver on the scaled
+        residual, to a tolerance that halves the distance to the bound (between ``rtol`` and 0.1), and
+        ``x += d``.  A well-conditioned system takes no step and gets the plain forward's bits.  A step
+        is guaranteed to gain only while 6e-8 times the condition number is below 1; past that it has
+        gained in practice (heat_bunny, 3.4e8: a factor of about 4 per step), and ``converged`` says
+        whether the bound was met.
+
+        Returns ``(iterations of all solves, converged, device solve time s)`` -- converged is the
+        true-residual bound -- and sets ``last_solve`` (``refinements``, ``relative_residual``, ``iters``
+        and ``residuals`` per solve).  ``refine=0`` with ``**kw`` (``return_history`` ...) is the plain forward and returns
+        what ``solver.solve`` returns."""
+        dev, dt = self.A_sys.ctx.torch_device, self.solver.torch_dtype
+        m = self.sampler.mask.reshape(-1).to(dt)
+        w = m * self.sample.matrix_scale + (1.0 - m)  # matrix_scale on free unknowns, 1 on masked ones
+        b = b.to(device=dev, dtype=dt)
+        if refine <= 0:
+            return self.solver.solve(b * w, x, rtol=rtol, max_iter=max_iter, **kw)
+        if kw:
+            raise ValueError(f"{sorted(kw)} belong to one solver.solve: pass refine=0 for the plain forward")
+        from .sparse import dot
+
+        it, conv, t = self.solver.solve(b * w, x, rtol=rtol, max_iter=max_iter)
+        iters = [it]
+        nb = float(np.sqrt(dot(b, b)))
+        r = self.residual(b, x)
+        nr = float(np.sqrt(dot(r, r)))
+        hist = [nr / nb if nb else 0.0]
+        while conv and nr > rtol * nb and len(iters) <= refine:
+            d = torch.zeros_like(x)
+            it, conv, ts = self.solver.solve(r * w, d, rtol=min(0.1, max(rtol, 0.5 * rtol * nb / nr)), max_iter=max_iter)
+            x += d
+            iters.append(it)
+            t += ts
+            r = self.residual(b, x)
+            nr = float(np.sqrt(dot(r, r)))
+            hist.append(nr / nb)
+        self.last_solve = {"refinements": len(iters) - 1, "relative_residual": hist[-1], "iters": iters,
+                           "residuals": hist}
+        return sum(iters), bool(conv and nr <= rtol * nb), t
 
 
 class ScaledInferenceWorkspace(SimpleInferenceWorkspace):
