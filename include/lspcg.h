@@ -521,6 +521,55 @@ int lspcg_graph_spai_loss(lspcg_graph* g, const void* Lvals, const void* Avals, 
                           const void* r, const void* mask, const void* diag, const int64_t* ptr, int64_t B, int kind,
                           double loss_eps, double* loss_out, void* dLvals);
 
+/* ---- P1 operators of a tetrahedral mesh, assembled on the device into a live matrix ----
+ * (the reference's pymathprim.geometry laplacian / lumped_mass as datagen/heat_tetmesh.py:17-56 and
+ * datagen/heat.py use them, and the linear-elastic block stiffness of datagen/elast_twist.py)
+ *
+ * lspcg_fem_create is the analysis, once per connectivity, all on the device.  nodes [N,3] fp64 and
+ * tets [T,4] int32, each a host or a device pointer (copied into the handle).
+ *   Pattern: the sorted unique (row, col) of the 16 vertex pairs of every tet plus (i, i) of every
+ *     vertex (an unused vertex owns a stored 0 diagonal): int32 indptr / indices, columns sorted, for
+ *     the scalar operator (n = N) and for the 3x3 block operator (nb = N) alike.
+ *   Gather map: per stored entry its contributions (tet, 4 a + b) in ascending tet order, within a
+ *     tet in ascending 4 a + b (one stable radix sort of 64-bit keys gives pattern and map at once).
+ *   Checks, one launch and one flag read back before anything else is built: a vertex index outside
+ *     0..N-1, a tet that repeats a vertex, a tet whose determinant is zero or not finite ->
+ *     LSPCG_ERR_FORMAT, the message names the first such tet, no handle is returned.  16 T + N, or
+ *     9 x the entry count, at or above 2^31 -> LSPCG_ERR_ARG.  N = 0 or T = 0 is legal (T = 0: the
+ *     diagonal entries only; N = 0: the empty matrix).
+ * Arithmetic, the same for every call below: per tet the expressions of a cofactor P1 element in
+ * double -- edge vectors a, b, c from vertex 0, det = (a0 (b×c)0 + a1 (b×c)1) + a2 (b×c)2,
+ * g1..g3 = b×c, c×a, a×b divided by det, g0 = -((g1 + g2) + g3), vol = |det| / 6 (either
+ * orientation) -- and every stored value is the left-to-right sum of its contributions in gather-map
+ * order, the mass term of a diagonal entry added last, rounded once to the matrix dtype on the store.
+ * No floating-point atomics: the bits depend on neither the grid nor earlier calls, and the result
+ * is symmetric bit for bit (blocks: out[(i,j)][p][q] == out[(j,i)][q][p]).
+ * The values are produced in scratch of the handle and handed to lspcg_mat_set_values with the
+ * handle's pattern: `out` must be a matrix of that pattern (block size 1 for heat, 3 for elasticity,
+ * fp32 or fp64), anything else returns LSPCG_ERR_FORMAT and nothing is written; a prepare_spmv copy
+ * is refilled, a solver on `out` needs lspcg_solver_update_matrix, exactly as after set_values.
+ * Calls on ONE fem handle must run on one stream at a time (the scratch is the handle's: the values
+ * of one assembly and, from the first heat call on, 17 doubles per tet of element matrices). */
+typedef struct lspcg_fem lspcg_fem;
+int lspcg_fem_create(lspcg_ctx* ctx, int64_t N, int64_t T, const double* nodes, const int32_t* tets, lspcg_fem** out);
+int lspcg_fem_destroy(lspcg_fem* f);
+/* moved vertices on the same connectivity (host or device [N,3] fp64); the determinant check runs
+ * again, and on LSPCG_ERR_FORMAT the old coordinates stay */
+int lspcg_fem_set_nodes(lspcg_fem* f, const double* nodes);
+int lspcg_fem_info(const lspcg_fem* f, int64_t* N, int64_t* T, int64_t* nnz);
+/* copy the pattern out (host or device destinations, N+1 and nnz int32; NULL skips an array) */
+int lspcg_fem_pattern(const lspcg_fem* f, int32_t* indptr, int32_t* indices);
+/* m_i = Σ_{t ∋ i} vol_t / 4 in ascending tet order; m: device fp64 [N] */
+int lspcg_fem_lumped_mass(lspcg_fem* f, double* m);
+/* A = K(κ) + diag(ρ ⊙ m): K_ab = ((g_a0 g_b0 + g_a1 g_b1) + g_a2 g_b2) · w, w = vol (kappa NULL) or
+ * vol · κ_t (kappa: device fp64 [T]); the diagonal's last term is ρ_i · m_i with ρ = density (device
+ * fp64 [N]) or, density NULL, density_scalar for every vertex (0: the bare Laplacian). */
+int lspcg_fem_heat(lspcg_fem* f, const double* kappa, const double* density, double density_scalar, lspcg_mat* out);
+/* Block (a,b)[i][j] += (λ (g_a,i g_b,j) + μ (g_a,j g_b,i + δ_ij g_a·g_b)) · vol with, per tet,
+ * λ = (E ν) / ((1 + ν)(1 − 2 ν)) and μ = E / (2 (1 + ν)) (young, poisson: device fp64 [T]);
+ * mass_coef · m_i is added last on the three diagonal entries of block (i, i).  Row-major blocks. */
+int lspcg_fem_elasticity(lspcg_fem* f, const double* young, const double* poisson, double mass_coef, lspcg_mat* out);
+
 /* ---- gradient clipping + optimizer step over a flat fp32 blob (neural_cg/utils/optim.py
  * create_optimizer: torch.optim.SGD / Adam / AdamW; Lightning's gradient_clip_val =
  * torch.nn.utils.clip_grad_norm_, config/trainer.yaml) ----

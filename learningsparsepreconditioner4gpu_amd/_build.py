@@ -27,7 +27,8 @@ LIB = PKG / "liblspcg_hip.so"
 OBJ = ROOT / "build" / "lspcg"
 SOURCES = ["lspcg_core.hip", "lspcg_pcg.hip", "lspcg_batch.hip", "lspcg_multi.hip", "lspcg_assemble.hip",
            "lspcg_gnn.hip", "lspcg_factor.hip", "lspcg_sell.hip", "lspcg_graph.hip", "lspcg_part.hip",
-           "lspcg_reorder.hip", "lspcg_gnn_bwd.hip", "lspcg_optim.hip", "lspcg_spectrum.hip", "lspcg_sample.hip"]
+           "lspcg_reorder.hip", "lspcg_gnn_bwd.hip", "lspcg_optim.hip", "lspcg_spectrum.hip", "lspcg_sample.hip",
+           "lspcg_fem.hip"]
 HEADERS = ["lspcg_internal.hpp", "lspcg_spmv.hpp", "lspcg_factor.hpp", "lspcg_sell.hpp", "lspcg_gnn.hpp",
            "lspcg_gnn_pack.hpp", "lspcg_pcg_kernels.hpp", "lspcg_pcg_parity.hpp", "lspcg_pcg_step.hpp", "lspcg_solver.hpp"]
 ARCH = os.environ.get("LSPCG_ARCH", "gfx950")

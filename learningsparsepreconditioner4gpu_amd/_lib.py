@@ -117,6 +117,14 @@ SIGNATURES = {
     "lspcg_graph_spmv_grad_vals": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
     "lspcg_graph_spai_loss": (C.c_int, [vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp, C.c_int64, C.c_int,
                                         C.c_double, vp, vp]),
+    "lspcg_fem_create": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, pp]),
+    "lspcg_fem_destroy": (C.c_int, [vp]),
+    "lspcg_fem_set_nodes": (C.c_int, [vp, vp]),
+    "lspcg_fem_info": (C.c_int, [vp, p_i64, p_i64, p_i64]),
+    "lspcg_fem_pattern": (C.c_int, [vp, vp, vp]),
+    "lspcg_fem_lumped_mass": (C.c_int, [vp, vp]),
+    "lspcg_fem_heat": (C.c_int, [vp, vp, vp, C.c_double, vp]),
+    "lspcg_fem_elasticity": (C.c_int, [vp, vp, vp, C.c_double, vp]),
     "lspcg_optim_step": (C.c_int, [vp, C.POINTER(lspcg_optim_desc), C.c_int64, C.c_int64, C.c_double, vp, vp, vp, vp,
                                    vp]),
     "lspcg_part_create": (C.c_int, [vp, vp, vp, vp, C.c_int64, vp, C.c_int64, pp]),

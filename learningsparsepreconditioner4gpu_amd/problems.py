@@ -262,20 +262,8 @@ def gaussian_random_field(points: np.ndarray, seed: int, len_scale: float = 1.0,
     return np.sqrt(2.0 / modes) * np.cos(points @ k.T + phi).sum(1)
 
 
-def heat_bunny(seed: int = 42, var: float = 0.99, eps: float = 1e-4, dirichlet: float = 0.05):
-    """BASELINE config 3 stand-in (``datagen/heat.py:22-96`` on ``bunny_low_res.obj``).
-
-    Mesh: Kuhn split (6 tets / cell) of every grid cell whose 8 corners lie inside the bunny
-    (``meshes/bunny_grid.npz``: winding-number voxelisation of the .obj, written by
-    ``tests/golden/make_golden.py bunny``) -- 6.3 k vertices against the reference's tetgen 6276.
-    Operator: ``L(κ_tet) + eps·M_lumped`` with ``κ_tet`` the per-tet mean (``to_tet_field``,
-    ``heat.py:15-19``) of a field renormalised as ``heat.py:83-86``.  Dirichlet: the lowest
-    ``dirichlet`` fraction of vertices by height (the reference's heat data has none; SURVEY 8(d)
-    adds them so the masked assembly is exercised).  Features: ``[field, x, y, z]`` -- the step's
-    field (``heat.py:96``) then the shared xyz (``:75-76``); make_data appends the mask: F_in = 5.
-
-    Returns ``(A_raw, mask[N,1], features[N,4])``.
-    """
+def bunny_tets() -> Tuple[np.ndarray, np.ndarray]:
+    """Vertices and tetrahedra of the bunny grid mesh (see ``heat_bunny``)."""
     z = np.load(MESH_DIR / "bunny_grid.npz")
     ins = z["inside"]
     h = float(z["h"])
@@ -290,6 +278,24 @@ def heat_bunny(seed: int = 42, var: float = 0.99, eps: float = 1e-4, dirichlet: 
     used, tets = np.unique(tets, return_inverse=True)
     tets = tets.reshape(-1, 4)
     nodes = z["lo"][None, :] + h * nodes[used]
+    return nodes, tets
+
+
+def heat_bunny(seed: int = 42, var: float = 0.99, eps: float = 1e-4, dirichlet: float = 0.05):
+    """BASELINE config 3 stand-in (``datagen/heat.py:22-96`` on ``bunny_low_res.obj``).
+
+    Mesh: Kuhn split (6 tets / cell) of every grid cell whose 8 corners lie inside the bunny
+    (``meshes/bunny_grid.npz``: winding-number voxelisation of the .obj, written by
+    ``tests/golden/make_golden.py bunny``) -- 6.3 k vertices against the reference's tetgen 6276.
+    Operator: ``L(κ_tet) + eps·M_lumped`` with ``κ_tet`` the per-tet mean (``to_tet_field``,
+    ``heat.py:15-19``) of a field renormalised as ``heat.py:83-86``.  Dirichlet: the lowest
+    ``dirichlet`` fraction of vertices by height (the reference's heat data has none; SURVEY 8(d)
+    adds them so the masked assembly is exercised).  Features: ``[field, x, y, z]`` -- the step's
+    field (``heat.py:96``) then the shared xyz (``:75-76``); make_data appends the mask: F_in = 5.
+
+    Returns ``(A_raw, mask[N,1], features[N,4])``.
+    """
+    nodes, tets = bunny_tets()
     field = gaussian_random_field(nodes, seed)
     field = field - field.min()
     field = field / (field.max() + 1e-4)
