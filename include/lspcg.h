@@ -200,9 +200,13 @@ int lspcg_spmv_variant_timed(lspcg_ctx* ctx, const lspcg_mat* A, int variant, co
 /* diagnostics: the same timing for the SELL-64 kernel the PCG loop uses (csrc/lspcg_sell.hpp) on a
  * SELL copy of A built inside the call (fp64 scalar CSR).  flags bit 0: store the values as fp32
  * (lossless only when every value is fp32-representable); bit 1: 16-bit column offsets where they
- * fit; bit 3: SELL-DIA where it fits (tried before bit 1); bit 2 (experiment): gather x from an
- * interleaved (x, x) pair array with one 16-B load per entry, the cost model of a fused update
- * evaluated in the gather.  y = A x, same bits as lspcg_spmv */
+ * fit; bit 3: SELL-DIA where it fits (tried before bit 1); bit 4 (with bit 1): SELL-64J (view kind
+ * 17) where 16-bit offsets fit, SELL-64 would store more than 1.15 x nnz slots and no row has more
+ * than 64 entries; bit 5 (with bit 4, without bit 2): SELL-64X (kind 18) on top of it from
+ * LSPCG_SELLX_MIN_N rows (default 262144) where every 256-row tile reads <= 256 x blocks; bit 2
+ * (experiment): gather x from an interleaved (x, x) pair array with one 16-B load per entry, the cost
+ * model of a fused update evaluated in the gather.  No padding limit applies.  y = A x, same bits as
+ * lspcg_spmv */
 int lspcg_spmv_sell_timed(lspcg_ctx* ctx, const lspcg_mat* A, int flags, const void* x, void* y,
                           int reps, int64_t flush_bytes, double* avg_ms);
 /* calibration: the same cold / warm timing for a plain streaming read of `bytes` (16-B loads, 8
@@ -392,6 +396,9 @@ int lspcg_batch_solve_coef(lspcg_batch* bt, const void* const* b, void* const* x
  * reports graphs_kept = 0. */
 int lspcg_batch_update(lspcg_batch* bt, const lspcg_mat* const* A, const lspcg_mat* const* L,
                        double epsilon, double* t_ms, int* graphs_kept);
+/* The iteration views of the batch's block-diagonal A (0), L (1), L^T (2), as lspcg_solver_views
+ * reports a solver's: col_kind[w], value_bytes[w]. */
+int lspcg_batch_views(const lspcg_batch* bt, int* col_kind, int* value_bytes);
 int lspcg_batch_destroy(lspcg_batch* bt);
 
 /* ---- spectrum of the preconditioned system from the PCG scalars (host only: no device call) ----

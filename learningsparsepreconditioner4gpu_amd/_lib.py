@@ -97,6 +97,7 @@ SIGNATURES = {
     "lspcg_batch_solve_coef": (C.c_int, [vp, pp, pp, C.c_double, C.c_int64, p_i64, p_i32, C.POINTER(p_f64), p_f64,
                                         C.POINTER(p_f64)]),
     "lspcg_batch_update": (C.c_int, [vp, pp, pp, C.c_double, p_f64, C.POINTER(C.c_int)]),
+    "lspcg_batch_views": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lspcg_batch_destroy": (C.c_int, [vp]),
     "lspcg_cg_lanczos": (C.c_int, [C.c_int64, p_f64, p_f64, p_f64]),
     "lspcg_tridiag_extremes": (C.c_int, [C.c_int64, p_f64, p_f64, p_f64, p_f64]),

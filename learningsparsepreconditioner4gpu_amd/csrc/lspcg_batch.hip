@@ -647,6 +647,11 @@ static int pad_d(lspcg_batch* bt) {
 
 extern "C" {
 
+int lspcg_batch_views(const lspcg_batch* bt, int* col_kind, int* value_bytes) {
+  LSPCG_CHECK(bt && bt->s, LSPCG_ERR_ARG, "batch_views: NULL argument");
+  return lspcg_solver_views(bt->s, col_kind, value_bytes);
+}
+
 int lspcg_batch_destroy(lspcg_batch* bt) {
   if (!bt) return LSPCG_OK;
   (void)hipSetDevice(bt->ctx->device);

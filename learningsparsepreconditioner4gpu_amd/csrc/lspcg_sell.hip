@@ -821,7 +821,7 @@ int sell_build_pattern(int64_t n, int64_t nnz, const int32_t* rowptr, const int3
   // irregular row lengths: the jagged layout stores ~1.1 x nnz instead
   if ((cols & kSellColJag) && fits16 && n && double(256) * double(P.groups) > kSellJagPad * double(nnz)) {
     if (int rc = jag_try(colind, st, &P, &taken)) return rc;
-    if (taken && (cols & kSellColXs) && n >= kSellXMinN) {  // stage each tile's x blocks in LDS where they fit
+    if (taken && (cols & kSellColXs) && n >= sellx_min_n()) {  // stage each tile's x blocks in LDS where they fit
       bool xs = false;
       if (int rc = xs_try(colind, st, &P, &xs)) return rc;
     }

@@ -110,7 +110,7 @@ constexpr int kSellXMax = 256;  // blocks per tile (32 KB of fp64)
 constexpr int kSellXBlk = 16;   // vector entries per staged block
 // smallest pattern staged: below it the per-tile staging latency and barriers cost more than the
 // gathers they replace (us per iteration, SELL-64X vs SELL-64J: delaunay1m 127.0 vs 134.9, delaunay64k
-// 31.5 vs 28.6, bunny 18.8 vs 16.9; profiles/r6_sellx_probe.jsonl)
+// 31.5 vs 28.6, bunny 18.8 vs 16.9; profiles/r6_sellx_probe.jsonl); sellx_min_n() is the floor in use
 constexpr int64_t kSellXMinN = 262144;
 // col_bits of the other layouts (with kSellJag / kSellJagX the `kind` numbers the C ABI reports)
 constexpr int kSellDia = 1;     // SELL-DIA, BSELL-DIA
@@ -1157,7 +1157,7 @@ namespace lspcg {
 //     <= 64 distinct offsets;
 //   SELL-64J (kSellColJag, 16-bit offsets fit) when SELL-64 would pad more than kSellJagPad x nnz and
 //     no row has more than 64 entries -- the only layout left past max_pad; SELL-64X on top of it
-//     (kSellColXs, n >= kSellXMinN) when every 256-row tile reads <= kSellXMax x blocks;
+//     (kSellColXs, n >= sellx_min_n()) when every 256-row tile reads <= kSellXMax x blocks;
 //   16-bit offsets (kSellCol16) when they fit, else int32 columns.
 // Host waits: one for the group total, one for (SELL-DIA fits, its slot total, 16-bit offsets fit)
 // together, then one per later attempt (two for SELL-64C when taken).  On failure *out is untouched.
@@ -1184,6 +1184,12 @@ inline bool sellc_allowed(int64_t n) {
   if (e && e[0] == '0') return false;
   const char* m = std::getenv("LSPCG_SELLC_MIN_N");
   return n >= (m ? std::atoll(m) : int64_t(400000));
+}
+// smallest pattern that gets SELL-64X (kSellXMinN; env LSPCG_SELLX_MIN_N moves the floor, read at
+// every pattern build: the tests lower it to reach the staged kernel at a few thousand rows)
+inline int64_t sellx_min_n() {
+  const char* m = std::getenv("LSPCG_SELLX_MIN_N");
+  return m ? std::atoll(m) : kSellXMinN;
 }
 inline bool bsdia_allowed() {
   const char* e = std::getenv("LSPCG_BSDIA");

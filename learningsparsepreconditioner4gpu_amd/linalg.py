@@ -101,6 +101,14 @@ def _copy_values(dst: DeviceMatrix, src: DeviceMatrix) -> None:
     dst.set_values(v, indptr=ip, indices=ix)
 
 
+def _views(fn: str, handle) -> dict:
+    """``lspcg_solver_views`` / ``lspcg_batch_views`` as ``{"A" | "L" | "LT": {"columns", "value_bytes"}}``."""
+    ck, vb = (C.c_int * 3)(), (C.c_int * 3)()
+    _lib.call(fn, handle, ck, vb)
+    names = {0: "csr", 1: "sdia", 8: "sellc", 16: "sell16", 17: "sell16j", 18: "sell16x", 32: "sell32"}
+    return {m: {"columns": names.get(ck[w], str(ck[w])), "value_bytes": vb[w]} for w, m in enumerate(("A", "L", "LT"))}
+
+
 MULTI_RHS_MAX = 8  # right-hand sides of one lspcg_solver_solve_multi call
 
 
@@ -258,11 +266,7 @@ class PreconditionedConjugateGradient:
         """The iteration views of A, L, Lᵀ (``lspcg_solver_views``): column storage (``"csr"``,
         ``"sdia"``, ``"sellc"`` (one-byte offset codes), ``"sell16"``, ``"sell32"``) and value bytes per
         slot (8, 4, or 1 = dictionary codes)."""
-        ck, vb = (C.c_int * 3)(), (C.c_int * 3)()
-        _lib.call("lspcg_solver_views", self.handle, ck, vb)
-        names = {0: "csr", 1: "sdia", 8: "sellc", 16: "sell16", 17: "sell16j", 18: "sell16x", 32: "sell32"}
-        return {m: {"columns": names.get(ck[w], str(ck[w])), "value_bytes": vb[w]}
-                for w, m in enumerate(("A", "L", "LT"))}
+        return _views("lspcg_solver_views", self.handle)
 
     @property
     def reorder_info(self) -> dict:
@@ -520,6 +524,12 @@ class BatchedConjugateGradient:
         if h is not None and h.value and _lib._lib is not None:
             _lib._lib.lspcg_batch_destroy(h)
             self.handle = None
+
+    @property
+    def views(self) -> dict:
+        """The iteration views of the block-diagonal A, L, Lᵀ (``lspcg_batch_views``), as
+        ``PreconditionedConjugateGradient.views`` reports a solver's."""
+        return _views("lspcg_batch_views", self.handle)
 
     def update(self, As=None, Ls=None, epsilon: Optional[float] = None) -> Tuple[float, bool]:
         """New values of A and / or L on this batch, same patterns (``lspcg_batch_update``): returns

@@ -184,12 +184,12 @@ def _dia_slots(A):
     return int(cnt.max()), int(cnt.sum())
 
 
-def _expected_kind(A, max_pad=2.0, dia=True, jag=True):
+def _expected_kind(A, max_pad=2.0, dia=True, jag=True, xs_min_n=262144):
     """lspcg_mat_prepare_spmv's rule: SELL-DIA (kind 1) if SELL-64's padded slots stay <= max_pad * nnz,
     every 64-row slice has <= 16 distinct offsets col - row and the slices' offset counts sum to no more
     than the 4-entry groups' slots (sorted rows); else, where 16-bit column offsets fit (every
     |col - 64*slice| <= 32767), SELL-64J (kind 17) when SELL-64 would pad more than 1.15 * nnz and no
-    row has more than 64 entries -- SELL-64X (18) when n >= 2^18 and every 256-row tile reads <= 256
+    row has more than 64 entries -- SELL-64X (18) when n >= xs_min_n (2^18; env LSPCG_SELLX_MIN_N) and every 256-row tile reads <= 256
     16-entry x blocks; else none (0) past max_pad; else 16-bit offsets or int32 columns."""
     n = A.shape[0]
     lens = np.diff(A.indptr)
@@ -208,7 +208,7 @@ def _expected_kind(A, max_pad=2.0, dia=True, jag=True):
     fit16 = bool(np.all(np.abs(off) <= 32767))
     if jag and fit16 and 256 * groups > 1.15 * A.nnz and lens.max() <= 64:
         key = np.unique((rows // 256) * (1 << 32) + A.indices.astype(np.int64) // 16)
-        return 18 if n >= 262144 and np.bincount(key >> 32).max() <= 256 else 17  # SELL-64X: large, tiles fit
+        return 18 if n >= xs_min_n and np.bincount(key >> 32).max() <= 256 else 17  # SELL-64X: large, tiles fit
     if overpad:
         return 0
     return 16 if fit16 else 32

@@ -68,6 +68,8 @@ SYSTEMS = {
     "sdia": (lambda: P.kuhn_laplacian(15), {}, 1, ("sdia",)),  # 3,375 rows: partial last slice, multi-kernel schedule
     "sell16": (_band, {}, 1, ("sell16",)),
     "sell16j": (lambda: P.delaunay_heat(4000)[0], {"LSPCG_REORDER": "0"}, 1, ("sell16j", "sell16x")),
+    # the x-staged jagged layout, which exists from 2^18 rows: its floor lowered to reach it at 4,000
+    "sell16x": (lambda: P.delaunay_heat(4000)[0], {"LSPCG_REORDER": "0", "LSPCG_SELLX_MIN_N": "0"}, 1, ("sell16x",)),
     "csr": (lambda: P.kuhn_laplacian(15), {"LSPCG_NO_SELL": "1"}, 1, ("csr",)),
     "small": (lambda: P.kuhn_laplacian(9), {}, 1, None),  # the one-workgroup solve
     "bsr3": (lambda: P.elasticity_box(6, 5, 5)[0], {"LSPCG_SMALL_N": "0"}, 3, None),
@@ -179,7 +181,7 @@ def _updated_equals_fresh(monkeypatch, name, pre, dtype, dot_order="compensated"
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("pre", KINDS)
-@pytest.mark.parametrize("name", ["sdia", "sell16", "sell16j", "csr", "small"])
+@pytest.mark.parametrize("name", ["sdia", "sell16", "sell16j", "sell16x", "csr", "small"])
 def test_updated_solver_equals_fresh_solver(gpu_ctx, monkeypatch, name, pre, dtype):
     _updated_equals_fresh(monkeypatch, name, pre, dtype)
 
